@@ -2,7 +2,7 @@
 """bench.py -- Groth16 proving throughput on MI355X (BASELINE.json metric: constraints/sec, BN254,
 2^20-constraint synthetic R1CS, at 1/2/4/8 GPUs).
 
-    python bench.py --gpus N --steps K --warmup W [--curve bn254|bls12_381] [--log-m 20]
+    python bench.py --gpus N --steps K --warmup W [--curve bn254|bls12_381] [--log-m 20] [--full] [--dump-outputs DIR]
     python bench.py --curve bls12_381 --log-m 24 --shards-in-process 8 [--full-parity]   config 5's data path on one GPU
     python bench.py --gpus 8 --dry-run                                                   the plan of an N-GPU run, no GPU touched
     (N > 1 without WORLD_SIZE in the environment re-executes itself under
@@ -16,7 +16,11 @@ window tables built once per key, outside the timed region, like any fixed CRS) 
 N > 1 is STRONG scaling of one proof (distributed-groth16_amd/parallel.py): each rank owns a 1/N slice of every
 MSM and of the h-polynomial's transforms; the exchanges run inside libdg16 over RCCL.
 
-One JSON line is printed by rank 0:
+One JSON line is printed by rank 0.  A plain run sets up, warms up, times the K steps and prints the headline: metric,
+value (constraints/s), unit, higher_is_better, dtype, ms_per_step (wall time of one timed step), steps, warmup and the
+configuration.  --dump-outputs DIR then writes the last timed proof as DIR/proof_{a,b,c}.npy (dump_outputs).  The
+figures below take runs or checks of their own and come only with --full:
+  single_proof_ms  the same step followed by a synchronisation, and the check that every queued proof equals it.
   roofline       the dominant kernel of the timed loop (G2 bucket accumulation, table mode), timed with HIP events
                  on the stream it runs on INSIDE the timed proofs: achieved = 160 B/point x points
                  per launch / duration, against the 8 TB/s HBM roof.  Small BY CONSTRUCTION (Pippenger does ~28 x W
@@ -291,6 +295,20 @@ def gpu_proof_affine(curve, proof_u8):
     gp = np.asarray(proof_u8).view(np.uint64)
     return (corc.jac_to_affine(curve, 1, gp[:3 * nl]), corc.jac_to_affine(curve, 2, gp[3 * nl:9 * nl]),
             corc.jac_to_affine(curve, 1, gp[9 * nl:]))
+
+
+def dump_outputs(ctx, curve, proof, out_dir):
+    """--dump-outputs: the proof the timed path hands its caller (A, C in G1, B in G2) as DIR/proof_{a,b,c}.npy.  The
+    library normalises each point to affine coordinates first (dg16_to_affine: the Jacobian representatives of one point
+    differ from run to run with the order of the additions inside a bucket); the coordinates' little-endian 32-bit limbs
+    are stored as float64, which holds them exactly, so two builds can be compared output for output."""
+    nl = FQ_BYTES[curve] // 8
+    jac = np.ascontiguousarray(proof.cpu().numpy()).view(np.uint64)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, group, part in (("proof_a", 1, jac[:3 * nl]), ("proof_b", 2, jac[3 * nl:9 * nl]),
+                              ("proof_c", 1, jac[9 * nl:])):
+        aff = ctx.to_affine(curve, group, part)
+        np.save(os.path.join(out_dir, name + ".npy"), aff.view(np.uint32).astype(np.float64))
 
 
 def prove_once(ctx, wl, rs=None):
@@ -966,10 +984,21 @@ def main():
     ap.add_argument("--transport", default="rccl", choices=["rccl", "torch", "python"],
                     help="N > 1: native RCCL communicator of libdg16 (default), torch.distributed under the native "
                          "pipeline, or the Python-driven protocol")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline figure: in-run calibration, rooflines, single_proof_ms and the "
+                         "queued-proof check, host-pointer step, extras, replicas (N > 1), CPU baseline and the oracle's "
+                         "parity gate.  Without it a run sets up, warms up, times the steps and prints the headline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last timed proof (A, B, C as affine coordinates, 32-bit "
+                         "limbs as float64) to DIR/proof_{a,b,c}.npy (rank 0)")
     args = ap.parse_args()
     curve = args.curve
+    if args.steps < 1:
+        raise SystemExit("--steps must be at least 1")
     if args.full_parity:
         args.cpu_sample_log = max(args.cpu_sample_log, args.log_m)
+    if args.shards_in_process and args.dump_outputs:
+        raise SystemExit("--dump-outputs writes the proof of the main timed path: not with --shards-in-process")
 
     if args.dry_run:
         print(json.dumps(dry_run_plan(curve, args.log_m, args.gpus, args.steps, args.warmup), indent=1))
@@ -1051,8 +1080,8 @@ def main():
     for _ in range(max(0, args.warmup - 1)):
         step()
     full_sync()
-    # the roof of THIS box in THIS run (every rank measures its own GPU; rank 0's figures go on the line)
-    calib = calibrate(local_rank)
+    # the roof of THIS box in THIS run (every rank measures its own GPU; rank 0's figures go on the line) -- --full only
+    calib = calibrate(local_rank) if args.full else None
     mad_peak = calib["mad_issue_T_lane_ops_per_s"] if calib else MAD_ISSUE_T
     for _ in range(1 if calib else 0):     # (one more untimed step: the calibration kernel evicted the proof's working set)
         step()
@@ -1077,81 +1106,9 @@ def main():
 
     ms_per_step = elapsed / args.steps * 1e3
     value = wl.nc * args.steps / elapsed
-    single_ms = None
-    if world == 1:
-        ts = []
-        for _ in range(min(args.steps, 5)):
-            t1 = time.perf_counter()
-            proof = step()
-            full_sync()
-            ts.append(time.perf_counter() - t1)
-        single_ms = sum(ts) / len(ts) * 1e3
-        # same inputs, same r and s: every queued proof must be the bytes of the synchronised one (which the oracle checks)
-        # (compared as affine points: the order of the additions inside a bucket is not fixed, so the Jacobian
-        # representatives of the same point may differ from run to run)
-        want = gpu_proof_affine(curve, proof.cpu().numpy())
-        bad = [i for i, q in enumerate(queued)
-               if not all(np.array_equal(x, y) for x, y in zip(gpu_proof_affine(curve, q.cpu().numpy()), want))]
-        if bad:
-            raise SystemExit("queued proofs %s differ from the synchronised proof" % bad)
-    del queued
-
-    # ---- dominant kernel: the G2 bucket accumulation of the LAST TIMED PROOF (HIP events recorded around it on
-    # the stream it ran on: dg16_last_kernel_ms, channel 2 = G2 accumulation, channel 1 = B1's G1 accumulation) ----
-    g2_acc_ms = ctx.last_kernel_ms(2, 1)
-    g1_acc_ms = ctx.last_kernel_ms(1, 1)            # B1's accumulation (A's runs beside B's G2 finalize)
-    # ... and the shader clock the chip held UNDER each of them, measured by the kernels themselves (ClkProbe, msm_impl.h):
-    # 16 lanes per SIMD-cycle x 4 SIMDs x CUs x that clock is the issue bound no DVFS state can move
-    g2_mhz = ctx.last_kernel_mhz(2) if hasattr(ctx, "last_kernel_mhz") else 0.0
-    g1_mhz = ctx.last_kernel_mhz(1) if hasattr(ctx, "last_kernel_mhz") else 0.0
-    n_cus = ctx.device_info()[1]
-
-    def cycle_view(mhz, mads_t, mads_per_add, slots_per_add):
-        if not mhz:
-            return None
-        bound = 16.0 * 4 * n_cus * mhz * 1e6 / 1e12
-        out = {"sclk_under_kernel_mhz": mhz, "issue_bound_at_kernel_clock_T": bound, "mads_frac_of_issue_bound": mads_t / bound}
-        if slots_per_add:
-            out["valu_slots_per_add"] = slots_per_add
-            out["all_valu_frac_of_issue_bound"] = mads_t * slots_per_add / mads_per_add / bound
-        return out
+    proof = queued[-1]
+    last_proof = proof.cpu()           # the last timed step's proof: what --dump-outputs writes at the end
     info = wl.pk.info()
-    n_g2 = info["n_ab"]                              # points of this rank's A / B1 / B launches (slice + 2 delta slots)
-    nwin = (SCALAR_BITS[curve] + 1 + info["c_ab"] - 1) // info["c_ab"]
-    g2_alg = {"bn254": 160.0, "bls12_381": 224.0}[curve]
-    g1_alg = {"bn254": 96.0, "bls12_381": 128.0}[curve]          # G1 affine point + 32-byte scalar
-    alg_bytes = g2_alg * n_g2
-    achieved = alg_bytes / (g2_acc_ms * 1e-3) / 1e9 if g2_acc_ms else 0.0
-    # one XYZZ mixed addition per nonzero digit, counted in the instruction that bounds it (add_mads)
-    g1_add_mads, g2_add_mads, mul_cost = add_mads(curve)
-    mads = float(g2_add_mads) * n_g2 * nwin
-    valu_t = mads / (g2_acc_ms * 1e-3) / 1e12 if g2_acc_ms else 0.0       # T v_mad_u64_u32 lane-op/s
-    _, mul_rate_g, mul_src = valu_constants(curve)   # measured G products/s of the C++-compiled product (auxiliary)
-    prods = proof_products(curve, info, args.log_m, wl.nc, world=world)
-    whole_t = prods["total"] / (ms_per_step * 1e-3) / 1e12     # per GPU: `prods` is this rank's share
-    g2_kernel = ("msm_accumulate_lds_kernel<Fp2<%s_fq>>" if curve == "bn254" else "msm_accumulate_steps_kernel<Fp2<%s_fq>>") % curve
-
-    # HBM traffic of that kernel: PMC counters cannot be read from inside the process; the committed summary of
-    # the separate rocprofv3 --pmc passes over the same launch (same curve, group, size) supplies it.
-    traffic, traffic_src, traffic_g1 = None, None, None
-    if curve == "bls12_381" and args.log_m == 20 and world == 1:
-        traffic, traffic_g1, traffic_src = pmc_traffic("bls12_381")
-    for name in ("r6_pmc_g2_accumulate.json", "r5_pmc_g2_accumulate.json", "r4v_pmc_g2_accumulate.json", "r4p_pmc_g2_accumulate.json", "r4l_pmc_g2_accumulate.json", "r4f_pmc_g2_accumulate.json", "r4a_pmc_g2_accumulate.json", "r3_pmc_g2_accumulate.json", "r2_pmc_g2_accumulate.json",
-                 "r1_pmc_g2_accumulate.json"):
-        pmc_path = os.path.join(ROOT, "profiles", name)
-        if args.log_m == 20 and curve == "bn254" and world == 1 and os.path.exists(pmc_path):
-            with open(pmc_path) as f:
-                pj = json.load(f)
-            traffic = pj["traffic_bytes_per_launch"]
-            traffic_g1 = pj.get("g1_traffic_bytes_per_launch")
-            traffic_src = "profiles/%s (2 x FETCH_SIZE + WRITE_SIZE, separate --pmc passes)" % name
-            break
-
-    # The peak is an instruction issue rate: a fraction above 1 can only mean a wrong count or a wrong clock.  The line is
-    # still printed (a timed run must not vanish in an accounting check), with the fact on it.
-    valu_over = valu_t > mad_peak * 1.0001 or whole_t > mad_peak
-    peak_src = ("in-run calibration (calibration.mad_issue_T_lane_ops_per_s of this line)" if calib else
-                "profiles/r1_ubench_instr_rate.txt (libdg16_calib.so not built)")
     rccl_ranks = prover.rccl_ranks() if hasattr(prover, "rccl_ranks") and world > 1 else None
     if rccl_ranks is not None and rccl_ranks != world:
         raise SystemExit("the RCCL communicator reports %s ranks, the job has %d" % (rccl_ranks, world))
@@ -1163,7 +1120,6 @@ def main():
         "steps": args.steps,
         "warmup": args.warmup,
         "ms_per_step": ms_per_step,
-        "single_proof_ms": single_ms,
         "higher_is_better": True,
         "scaling": "strong",
         "vs_baseline": None,
@@ -1183,58 +1139,136 @@ def main():
                    "key_table_build_s": wl.pk_build_s, "first_proof_s": first_proof_s,
                    "time_to_first_proof_s": wl.pk_build_s + first_proof_s,
                    "key_window_bits": {"ab": info["c_ab"], "l": info["c_l"], "h": info["c_h"]}},
-        "roofline": {"bound": "hbm", "kernel": g2_kernel + " (G2 bucket accumulation, table mode, inside the "
-                     "timed proofs)", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                     "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": traffic_src,
-                     "kernel_ms": g2_acc_ms, "points_per_launch": n_g2,
-                     "note": "%d B/point algorithmic (each point and scalar once); Pippenger gathers every point once "
-                             "per window, which is what the PMC traffic shows -- the kernel is integer-VALU-bound "
-                             "(see valu_roofline)" % int(g2_alg)},
-        "calibration": calib,
-        "valu_roofline": {"unit": "T v_mad_u64_u32 lane-op/s", "achieved": valu_t, "peak": mad_peak,
-                          "frac": valu_t / mad_peak, "peak_source": peak_src,
-                          "frac_vs_round1_constant": valu_t / MAD_ISSUE_T,
-                          "cycle_view": cycle_view(g2_mhz, valu_t, g2_add_mads, {"bn254": 5900}.get(curve)),
-                          "mads_per_g1_add": g1_add_mads, "mads_per_g2_add": g2_add_mads, "mads_per_product": mul_cost,
-                          "product_equivalents_G_per_s": valu_t * 1e3 / mul_cost,
-                          "measured_product_rate_G_per_s": mul_rate_g, "measured_product_rate_source": mul_src,
-                          "whole_proof_mads": prods, "whole_proof_achieved": whole_t,
-                          "whole_proof_valu_frac": whole_t / mad_peak,
-                          "exceeds_peak": valu_over,
-                          "note": "%d v_mad_u64_u32 per G2 mixed add x %d points x %d windows / kernel time against the "
-                                  "chip-wide issue rate of that instruction (%.1f T lane-op/s: the bound no rewrite of the "
-                                  "product can move).  product_equivalents = achieved / %d mads; measured_product_rate = "
-                                  "tools/ubench/fe_rate (a dependent chain of the library's own product per lane). "
-                                  "whole_proof_* = every v_mad_u64_u32 a proof must issue (per GPU) / ms_per_step: the "
-                                  "headroom of the whole pipeline, not of one kernel"
-                                  % (g2_add_mads, n_g2, nwin, mad_peak, mul_cost)},
-        "g1_accumulate_ms": g1_acc_ms,
-        # the G1 accumulation: four launches per proof (A, B1, L, H), more TOTAL time than the G2 launch and further from
-        # the issue roof -- on the line next to the G2 figures since round 5
-        "roofline_g1": {"bound": "hbm", "kernel": "msm_accumulate_kernel<Fp<%s_fq>> (B1's G1 bucket accumulation, table mode, "
-                        "inside the timed proofs; B1, L, H are launches of the same kernel)" % curve,
-                        "achieved": (g1_alg * n_g2 / (g1_acc_ms * 1e-3) / 1e9) if g1_acc_ms else 0.0, "peak": HBM_PEAK_GBS,
-                        "unit": "GB/s", "frac": (g1_alg * n_g2 / (g1_acc_ms * 1e-3) / 1e9 / HBM_PEAK_GBS) if g1_acc_ms else 0.0,
-                        "traffic": traffic_g1, "traffic_source": traffic_src,
-                        "kernel_ms": g1_acc_ms, "points_per_launch": n_g2, "launches_per_proof": 4,
-                        "note": "%d B/point algorithmic (point + scalar once)" % int(g1_alg)},
-        "valu_roofline_g1": {"unit": "T v_mad_u64_u32 lane-op/s",
-                             "achieved": (float(g1_add_mads) * n_g2 * nwin / (g1_acc_ms * 1e-3) / 1e12) if g1_acc_ms else 0.0,
-                             "peak": mad_peak, "peak_source": peak_src,
-                             "frac": (float(g1_add_mads) * n_g2 * nwin / (g1_acc_ms * 1e-3) / 1e12 / mad_peak) if g1_acc_ms else 0.0,
-                             "mads_per_g1_add": g1_add_mads,
-                             "valu_slots_per_g1_add": {"bn254": 2089}.get(curve),
-                             "cycle_view": cycle_view(g1_mhz, (float(g1_add_mads) * n_g2 * nwin / (g1_acc_ms * 1e-3) / 1e12) if g1_acc_ms else 0.0,
-                                                      g1_add_mads, {"bn254": 2089}.get(curve)),
-                             "note": "every integer VALU instruction of the loop (mads, column shifts / masks, m[k] products) "
-                                     "issues at about the same ~35 T lane-op/s (profiles/r5c_ubench_instr_rate.txt): the "
-                                     "loop's 2089 issue slots per addition, not its 1467 mads, are what the time buys -- "
-                                     "SQ counters (profiles/r5a_pmc_sq_bn254.md): VALU busy 74 % of the cycles at the nominal "
-                                     "2.4 GHz = 83 % at the ~2.13 GHz the chip holds under this kernel "
-                                     "(profiles/r5c_clock_under_kernels.txt)"},
-        "host": {"cpu_model": cpu_model(), "nproc": os.cpu_count()},
     }
-    if world > 1 and not args.no_replicas:
+    if args.full:
+        single_ms = None
+        if world == 1:
+            ts = []
+            for _ in range(min(args.steps, 5)):
+                t1 = time.perf_counter()
+                proof = step()
+                full_sync()
+                ts.append(time.perf_counter() - t1)
+            single_ms = sum(ts) / len(ts) * 1e3
+            # same inputs, same r and s: every queued proof must be the bytes of the synchronised one (which the oracle checks)
+            # (compared as affine points: the order of the additions inside a bucket is not fixed, so the Jacobian
+            # representatives of the same point may differ from run to run)
+            want = gpu_proof_affine(curve, proof.cpu().numpy())
+            bad = [i for i, q in enumerate(queued)
+                   if not all(np.array_equal(x, y) for x, y in zip(gpu_proof_affine(curve, q.cpu().numpy()), want))]
+            if bad:
+                raise SystemExit("queued proofs %s differ from the synchronised proof" % bad)
+        del queued
+
+        # ---- dominant kernel: the G2 bucket accumulation of the LAST TIMED PROOF (HIP events recorded around it on
+        # the stream it ran on: dg16_last_kernel_ms, channel 2 = G2 accumulation, channel 1 = B1's G1 accumulation) ----
+        g2_acc_ms = ctx.last_kernel_ms(2, 1)
+        g1_acc_ms = ctx.last_kernel_ms(1, 1)            # B1's accumulation (A's runs beside B's G2 finalize)
+        # ... and the shader clock the chip held UNDER each of them, measured by the kernels themselves (ClkProbe, msm_impl.h):
+        # 16 lanes per SIMD-cycle x 4 SIMDs x CUs x that clock is the issue bound no DVFS state can move
+        g2_mhz = ctx.last_kernel_mhz(2) if hasattr(ctx, "last_kernel_mhz") else 0.0
+        g1_mhz = ctx.last_kernel_mhz(1) if hasattr(ctx, "last_kernel_mhz") else 0.0
+        n_cus = ctx.device_info()[1]
+
+        def cycle_view(mhz, mads_t, mads_per_add, slots_per_add):
+            if not mhz:
+                return None
+            bound = 16.0 * 4 * n_cus * mhz * 1e6 / 1e12
+            out = {"sclk_under_kernel_mhz": mhz, "issue_bound_at_kernel_clock_T": bound, "mads_frac_of_issue_bound": mads_t / bound}
+            if slots_per_add:
+                out["valu_slots_per_add"] = slots_per_add
+                out["all_valu_frac_of_issue_bound"] = mads_t * slots_per_add / mads_per_add / bound
+            return out
+        n_g2 = info["n_ab"]                              # points of this rank's A / B1 / B launches (slice + 2 delta slots)
+        nwin = (SCALAR_BITS[curve] + 1 + info["c_ab"] - 1) // info["c_ab"]
+        g2_alg = {"bn254": 160.0, "bls12_381": 224.0}[curve]
+        g1_alg = {"bn254": 96.0, "bls12_381": 128.0}[curve]          # G1 affine point + 32-byte scalar
+        alg_bytes = g2_alg * n_g2
+        achieved = alg_bytes / (g2_acc_ms * 1e-3) / 1e9 if g2_acc_ms else 0.0
+        # one XYZZ mixed addition per nonzero digit, counted in the instruction that bounds it (add_mads)
+        g1_add_mads, g2_add_mads, mul_cost = add_mads(curve)
+        mads = float(g2_add_mads) * n_g2 * nwin
+        valu_t = mads / (g2_acc_ms * 1e-3) / 1e12 if g2_acc_ms else 0.0       # T v_mad_u64_u32 lane-op/s
+        _, mul_rate_g, mul_src = valu_constants(curve)   # measured G products/s of the C++-compiled product (auxiliary)
+        prods = proof_products(curve, info, args.log_m, wl.nc, world=world)
+        whole_t = prods["total"] / (ms_per_step * 1e-3) / 1e12     # per GPU: `prods` is this rank's share
+        g2_kernel = ("msm_accumulate_lds_kernel<Fp2<%s_fq>>" if curve == "bn254" else "msm_accumulate_steps_kernel<Fp2<%s_fq>>") % curve
+
+        # HBM traffic of that kernel: PMC counters cannot be read from inside the process; the committed summary of
+        # the separate rocprofv3 --pmc passes over the same launch (same curve, group, size) supplies it.
+        traffic, traffic_src, traffic_g1 = None, None, None
+        if curve == "bls12_381" and args.log_m == 20 and world == 1:
+            traffic, traffic_g1, traffic_src = pmc_traffic("bls12_381")
+        for name in ("r6_pmc_g2_accumulate.json", "r5_pmc_g2_accumulate.json", "r4v_pmc_g2_accumulate.json", "r4p_pmc_g2_accumulate.json", "r4l_pmc_g2_accumulate.json", "r4f_pmc_g2_accumulate.json", "r4a_pmc_g2_accumulate.json", "r3_pmc_g2_accumulate.json", "r2_pmc_g2_accumulate.json",
+                     "r1_pmc_g2_accumulate.json"):
+            pmc_path = os.path.join(ROOT, "profiles", name)
+            if args.log_m == 20 and curve == "bn254" and world == 1 and os.path.exists(pmc_path):
+                with open(pmc_path) as f:
+                    pj = json.load(f)
+                traffic = pj["traffic_bytes_per_launch"]
+                traffic_g1 = pj.get("g1_traffic_bytes_per_launch")
+                traffic_src = "profiles/%s (2 x FETCH_SIZE + WRITE_SIZE, separate --pmc passes)" % name
+                break
+
+        # The peak is an instruction issue rate: a fraction above 1 can only mean a wrong count or a wrong clock.  The line is
+        # still printed (a timed run must not vanish in an accounting check), with the fact on it.
+        valu_over = valu_t > mad_peak * 1.0001 or whole_t > mad_peak
+        peak_src = ("in-run calibration (calibration.mad_issue_T_lane_ops_per_s of this line)" if calib else
+                    "profiles/r1_ubench_instr_rate.txt (libdg16_calib.so not built)")
+        res["single_proof_ms"] = single_ms
+        res.update({
+            "roofline": {"bound": "hbm", "kernel": g2_kernel + " (G2 bucket accumulation, table mode, inside the "
+                         "timed proofs)", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                         "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": traffic_src,
+                         "kernel_ms": g2_acc_ms, "points_per_launch": n_g2,
+                         "note": "%d B/point algorithmic (each point and scalar once); Pippenger gathers every point once "
+                                 "per window, which is what the PMC traffic shows -- the kernel is integer-VALU-bound "
+                                 "(see valu_roofline)" % int(g2_alg)},
+            "calibration": calib,
+            "valu_roofline": {"unit": "T v_mad_u64_u32 lane-op/s", "achieved": valu_t, "peak": mad_peak,
+                              "frac": valu_t / mad_peak, "peak_source": peak_src,
+                              "frac_vs_round1_constant": valu_t / MAD_ISSUE_T,
+                              "cycle_view": cycle_view(g2_mhz, valu_t, g2_add_mads, {"bn254": 5900}.get(curve)),
+                              "mads_per_g1_add": g1_add_mads, "mads_per_g2_add": g2_add_mads, "mads_per_product": mul_cost,
+                              "product_equivalents_G_per_s": valu_t * 1e3 / mul_cost,
+                              "measured_product_rate_G_per_s": mul_rate_g, "measured_product_rate_source": mul_src,
+                              "whole_proof_mads": prods, "whole_proof_achieved": whole_t,
+                              "whole_proof_valu_frac": whole_t / mad_peak,
+                              "exceeds_peak": valu_over,
+                              "note": "%d v_mad_u64_u32 per G2 mixed add x %d points x %d windows / kernel time against the "
+                                      "chip-wide issue rate of that instruction (%.1f T lane-op/s: the bound no rewrite of the "
+                                      "product can move).  product_equivalents = achieved / %d mads; measured_product_rate = "
+                                      "tools/ubench/fe_rate (a dependent chain of the library's own product per lane). "
+                                      "whole_proof_* = every v_mad_u64_u32 a proof must issue (per GPU) / ms_per_step: the "
+                                      "headroom of the whole pipeline, not of one kernel"
+                                      % (g2_add_mads, n_g2, nwin, mad_peak, mul_cost)},
+            "g1_accumulate_ms": g1_acc_ms,
+            # the G1 accumulation: four launches per proof (A, B1, L, H), more TOTAL time than the G2 launch and further from
+            # the issue roof -- on the line next to the G2 figures since round 5
+            "roofline_g1": {"bound": "hbm", "kernel": "msm_accumulate_kernel<Fp<%s_fq>> (B1's G1 bucket accumulation, table mode, "
+                            "inside the timed proofs; B1, L, H are launches of the same kernel)" % curve,
+                            "achieved": (g1_alg * n_g2 / (g1_acc_ms * 1e-3) / 1e9) if g1_acc_ms else 0.0, "peak": HBM_PEAK_GBS,
+                            "unit": "GB/s", "frac": (g1_alg * n_g2 / (g1_acc_ms * 1e-3) / 1e9 / HBM_PEAK_GBS) if g1_acc_ms else 0.0,
+                            "traffic": traffic_g1, "traffic_source": traffic_src,
+                            "kernel_ms": g1_acc_ms, "points_per_launch": n_g2, "launches_per_proof": 4,
+                            "note": "%d B/point algorithmic (point + scalar once)" % int(g1_alg)},
+            "valu_roofline_g1": {"unit": "T v_mad_u64_u32 lane-op/s",
+                                 "achieved": (float(g1_add_mads) * n_g2 * nwin / (g1_acc_ms * 1e-3) / 1e12) if g1_acc_ms else 0.0,
+                                 "peak": mad_peak, "peak_source": peak_src,
+                                 "frac": (float(g1_add_mads) * n_g2 * nwin / (g1_acc_ms * 1e-3) / 1e12 / mad_peak) if g1_acc_ms else 0.0,
+                                 "mads_per_g1_add": g1_add_mads,
+                                 "valu_slots_per_g1_add": {"bn254": 2089}.get(curve),
+                                 "cycle_view": cycle_view(g1_mhz, (float(g1_add_mads) * n_g2 * nwin / (g1_acc_ms * 1e-3) / 1e12) if g1_acc_ms else 0.0,
+                                                          g1_add_mads, {"bn254": 2089}.get(curve)),
+                                 "note": "every integer VALU instruction of the loop (mads, column shifts / masks, m[k] products) "
+                                         "issues at about the same ~35 T lane-op/s (profiles/r5c_ubench_instr_rate.txt): the "
+                                         "loop's 2089 issue slots per addition, not its 1467 mads, are what the time buys -- "
+                                         "SQ counters (profiles/r5a_pmc_sq_bn254.md): VALU busy 74 % of the cycles at the nominal "
+                                         "2.4 GHz = 83 % at the ~2.13 GHz the chip holds under this kernel "
+                                         "(profiles/r5c_clock_under_kernels.txt)"},
+            "host": {"cpu_model": cpu_model(), "nproc": os.cpu_count()},
+        })
+    if args.full and world > 1 and not args.no_replicas:
         # Secondary figure, labelled as such: N INDEPENDENT proofs, one whole resident key and one whole proof per
         # GPU, no exchange at all (what a proving service with many statements in flight would run).  Weak scaling.
         rwl = Workload(ctx, dev, args.log_m, 0, 1, curve=curve, seed=20 + rank)
@@ -1260,11 +1294,11 @@ def main():
                            "value": world * rwl.nc * args.steps / rel, "unit": "constraints/s", "scaling": "weak",
                            "ms_per_step": rel / args.steps * 1e3, "key_table_bytes_per_gpu": rwl.pk.info()["table_bytes"]}
         rwl.pk.close()
-    if rank == 0 and world == 1:
+    if args.full and rank == 0 and world == 1:
         res["host_pointer_step"] = host_pointer_figure(ctx, wl, prover, min(args.steps, 10))
-    if rank == 0 and world == 1 and not args.no_extras:
+    if args.full and rank == 0 and world == 1 and not args.no_extras:
         extras(ctx, dev, wl, curve, res)
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         if args.log_m <= args.cpu_sample_log:
             cb, ok = cpu_baseline_and_parity(ctx, dev, args.log_m, curve, wl=wl, gpu_proof=proof.cpu().numpy())
         else:       # e.g. 2^24: prove a bounded 2^cpu_sample_log instance on both sides instead
@@ -1281,7 +1315,7 @@ def main():
         if not ok:
             print(json.dumps(res))
             raise SystemExit("GPU proof differs from the oracle proof")
-    if rank == 0 and world > 1 and not args.no_cpu_baseline and args.log_m <= args.cpu_sample_log:
+    if args.full and rank == 0 and world > 1 and not args.no_cpu_baseline and args.log_m <= args.cpu_sample_log:
         # live parity gate of the distributed proof: the oracle proves the timed instance on rank 0's host cores
         # (checker only: cpu_baseline is reported at N = 1)
         _, ok = cpu_baseline_and_parity(ctx, dev, args.log_m, curve, wl=wl, gpu_proof=proof.cpu().numpy())
@@ -1289,6 +1323,8 @@ def main():
         if not ok:
             print(json.dumps(res))
             raise SystemExit("distributed GPU proof differs from the oracle proof")
+    if args.dump_outputs and rank == 0:
+        dump_outputs(ctx, curve, last_proof, args.dump_outputs)
     if rank == 0:
         print(json.dumps(res))
     prover.close()

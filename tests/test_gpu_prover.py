@@ -292,3 +292,32 @@ def test_queue_of_proofs_with_overlapped_tail(curve, log_m):
         want = bench.gpu_proof_affine(curve, refs[k])
         assert all(np.array_equal(g, w_) for g, w_ in zip(got, want)), "queued proof %d" % k
     wl.pk.close()
+
+
+def test_bench_plain_line_and_dumped_proof(tmp_path):
+    """`bench.py` without --full: the headline line (steps = the timed steps, ms_per_step) and nothing that needs a run
+    of its own; --dump-outputs writes the last timed proof, which must be the oracle's proof of the bench's instance
+    (bench.Workload, seed 20) -- affine coordinates, 32-bit limbs as float64."""
+    import json
+    import os
+    import subprocess
+    import sys
+    import torch
+    import bench
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--log-m", "12",
+           "--dump-outputs", str(tmp_path)]
+    out = subprocess.run(cmd, cwd=root, capture_output=True, text=True, timeout=280)
+    assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-4000:]
+    d = json.loads([ln for ln in out.stdout.splitlines() if ln.startswith("{")][-1])
+    assert d["metric"] == "groth16_constraints_per_sec" and d["unit"] == "constraints/s" and d["higher_is_better"]
+    assert d["steps"] == 3 and d["warmup"] == 1 and d["ms_per_step"] > 0 and d["dtype"] == "u32"
+    assert abs(d["value"] - ((1 << 12) - 2) / (d["ms_per_step"] * 1e-3)) <= 1e-6 * d["value"]
+    assert not {"calibration", "roofline", "cpu_baseline", "parity_check", "host_pointer_step"} & set(d)
+    wl = bench.Workload(ctx(), torch.device("cuda", 0), 12, curve="bn254")
+    (A, B, C), _ = bench.oracle_prove(wl, bench.cpu_threads())
+    wl.pk.close()
+    for name, want in (("proof_a", A), ("proof_b", B), ("proof_c", C)):
+        got = np.load(os.path.join(str(tmp_path), name + ".npy"))
+        assert got.dtype == np.float64
+        assert np.array_equal(got.astype(np.uint32).view(np.uint64).reshape(-1), np.asarray(want).reshape(-1)), name

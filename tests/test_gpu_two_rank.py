@@ -46,7 +46,7 @@ def test_bench_flow_with_two_ranks_on_one_device(transport):
     (parallel.make_prover's collective decision) instead of issuing mismatched collectives."""
     import json
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--log-m", "14",
-           "--transport", transport]
+           "--transport", transport, "--full"]
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", DG16_BENCH_SINGLE_DEVICE="1")
     env.pop("WORLD_SIZE", None)
     out = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=280)

@@ -17,7 +17,7 @@ done
 for pass in 1 2; do
   for v in $names; do
     lib=distributed-groth16_amd/libdg16_$v.so; [ $v = base ] && lib=distributed-groth16_amd/libdg16.so
-    DG16_LIB=$PWD/$lib timeout 200 python bench.py --steps $steps --warmup 3 --no-extras --no-cpu-baseline 2> $O/bench_$v.err | tee -a $O/bench_$v.jsonl | python -c "
+    DG16_LIB=$PWD/$lib timeout 200 python bench.py --steps $steps --warmup 3 --full --no-extras --no-cpu-baseline 2> $O/bench_$v.err | tee -a $O/bench_$v.jsonl | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('$v pass $pass: ms_per_proof %.3f g2_acc_ms %.3f g1_acc_ms %.3f parity %s' % (d['ms_per_step'], d['roofline']['kernel_ms'], d['g1_accumulate_ms'], d['parity_check']))" | tee -a $O/summary.txt
   done

@@ -17,9 +17,9 @@ git_head=$(cat .git_head 2>/dev/null || echo unknown)
 timeout 900 python -X faulthandler -m pytest $sel -m gpu -q -o faulthandler_timeout=400 > $O/gputest_full.txt 2>&1
 (grep -E "passed|failed|error|Fatal|File \"/root/repo|File \"/tmp/code" $O/gputest_full.txt | tail -30; grep -E "^tests/|^\.+|^=+" $O/gputest_full.txt | tail -12) > $O/gputest.txt
 tail -3 $O/gputest.txt
-(timeout 300 python bench.py --steps 20 --warmup 3) > $O/bench_line.json 2> $O/bench.err
+(timeout 300 python bench.py --steps 20 --warmup 3 --full) > $O/bench_line.json 2> $O/bench.err
 rm -rf $O/prof
-timeout 200 rocprofv3 --kernel-trace --stats -d $O/prof -o run -- python bench.py --steps 10 --warmup 2 --no-extras --no-cpu-baseline > $O/bench_line_profiled_run.json 2> $O/prof.err
+timeout 200 rocprofv3 --kernel-trace --stats -d $O/prof -o run -- python bench.py --steps 10 --warmup 2 --full --no-extras --no-cpu-baseline > $O/bench_line_profiled_run.json 2> $O/prof.err
 db=$(find $O/prof -name "*.db" | head -1)
 python tools/rocprof_stats.py "$db" $O/bench_prove_2e20_kernel_stats.md > /dev/null
 python tools/rocprof_timeline.py "$db" 14 $O/timeline_one_proof.md > /dev/null 2>&1
@@ -43,7 +43,7 @@ done
 python tools/pmc_json.py $O/pmc_raw_bls12_381.txt "$tag" bls12_381 > $O/pmc_bls12_381_accumulate.json
 # config 5's curve and data path: BLS12-381 2^20 (timed, parity on the timed instance) and the sharded proof over 8 shard
 # keys in this process against the oracle
-(timeout 300 python bench.py --curve bls12_381 --log-m 20 --steps 5 --warmup 2 --no-extras) > $O/bench_line_bls12_381_2e20.json 2>> $O/bench.err
+(timeout 300 python bench.py --curve bls12_381 --log-m 20 --steps 5 --warmup 2 --full --no-extras) > $O/bench_line_bls12_381_2e20.json 2>> $O/bench.err
 (timeout 300 python bench.py --curve bls12_381 --log-m 20 --shards-in-process 8 --steps 3) > $O/bench_shards_in_process_bls12_381_2e20.json 2>> $O/bench.err
 (timeout 120 python tools/shard_timing.py 20 10 bn254 1,2,4,8 2>&1 | grep -E "^world|per_rank") > $O/shard_timing.txt
 (DG16_OVERLAP=1 timeout 120 python tools/shard_timing.py 20 10 bn254 1,2,4,8 2>&1 | grep -E "^world|per_rank") >> $O/shard_timing.txt

@@ -16,7 +16,7 @@ if [ -f $P ]; then
   done
   for v in new prev; do
     l=""; [ $v = prev ] && l="DG16_LIB=$P"
-    env $l timeout 200 python bench.py --steps 20 --warmup 3 --no-extras --no-cpu-baseline 2>/dev/null | python -c "
+    env $l timeout 200 python bench.py --steps 20 --warmup 3 --full --no-extras --no-cpu-baseline 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('$v bn254 proof ms', round(d['ms_per_step'],3), 'single', round(d['single_proof_ms'],3), d['parity_check'])" >> $O/ab.txt
   done
@@ -27,7 +27,7 @@ cat $O/repro.txt
 timeout 600 python -X faulthandler -m pytest tests -m gpu -q -o faulthandler_timeout=400 > $O/gputest_full.txt 2>&1
 (grep -E "passed|failed|error|Fatal|File \"/root/repo|File \"/tmp/code" $O/gputest_full.txt | tail -30; grep -E "^tests/|^\.+|^=+" $O/gputest_full.txt | tail -12) > $O/gputest.txt
 tail -3 $O/gputest.txt
-(timeout 300 python bench.py --steps 20 --warmup 3) > $O/bench_line.json 2> $O/bench.err
+(timeout 300 python bench.py --steps 20 --warmup 3 --full) > $O/bench_line.json 2> $O/bench.err
 python - "$O" <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[1] + '/bench_line.json').read().strip().splitlines()[-1])
