@@ -92,7 +92,7 @@ inline unsigned msm_window_bits(size_t n, bool table, unsigned scalar_bits = 0) 
 //   sum_w d_w 2^(c w) P = sum_{j < k} 2^(c j) sum_r d_{k r + j} (2^(c k r) P)
 inline MsmGeom msm_geometry(size_t n, unsigned scalar_bits, bool table = false, unsigned c_fixed = 0, unsigned stride = 1) {
   MsmGeom g;
-  g.c = c_fixed ? c_fixed : msm_window_bits(n, table);
+  g.c = c_fixed ? c_fixed : msm_window_bits(n, table, table ? scalar_bits : 0);   // a table's own width (msm_window_bits)
   g.nwin = (scalar_bits + 1 + g.c - 1) / g.c;   // one spare bit absorbs the last carry
   g.log_nb = g.c - 1;
   g.table = table ? 1u : 0u;
