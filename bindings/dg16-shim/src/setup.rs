@@ -1,0 +1,98 @@
+//! Key generation: `Groth16::<E, CircomReduction>::circuit_specific_setup(circuit, rng)` (groth16/examples/sha256.rs:137,
+//! million.rs:137, d_sha256.rs:138, mpc-api/src/main.rs:151) from the point where the constraint matrices exist, as ONE
+//! call of `dg16_groth16_setup` (which runs `FixedBase::msm`'s job through `dg16_fixed_base_mul`'s kernels).
+//!
+//! Like the rest of this crate: never compiled here (bindings/README.md) -- source for a maintainer's box with cargo.
+use crate::pack::{pack_affine, scalars_as_bytes, FieldBytes};
+use crate::prove::Csr;
+use crate::{check, sys, Dg16Config, Dg16Error, CTX};
+use ark_ec::pairing::Pairing;
+use ark_ec::short_weierstrass::{Affine, SWCurveConfig};
+use ark_ec::AffineRepr;
+use ark_ff::{BigInteger, PrimeField, UniformRand, Zero};
+use ark_groth16::{ProvingKey, VerifyingKey};
+use ark_relations::r1cs::ConstraintMatrices;
+use ark_std::rand::RngCore;
+
+/// x || y Montgomery limbs with the identity as zeros (the library's output layout) -> `Affine<P>`.
+fn unpack_affine<P: SWCurveConfig>(buf: &[u8]) -> Vec<Affine<P>>
+where
+    P::BaseField: FieldBytes,
+{
+    let fe = <P::BaseField as FieldBytes>::BYTES;
+    buf.chunks_exact(2 * fe)
+        .map(|c| {
+            if c.iter().all(|b| *b == 0) {
+                Affine::<P>::zero()
+            } else {
+                Affine::<P>::new_unchecked(<P::BaseField>::read_mont(&c[..fe]), <P::BaseField>::read_mont(&c[fe..]))
+            }
+        })
+        .collect()
+}
+
+/// `generate_random_parameters_with_reduction` with the library doing everything after the trapdoor is drawn.
+/// `num_inputs` counts the constant 1 (`matrices.num_instance_variables`).
+pub fn circuit_specific_setup<E, P1, P2, R: RngCore>(m: &ConstraintMatrices<E::ScalarField>, rng: &mut R)
+    -> Result<ProvingKey<E>, Dg16Error>
+where
+    E: Pairing<G1Affine = Affine<P1>, G2Affine = Affine<P2>>,
+    P1: Dg16Config<ScalarField = E::ScalarField>,
+    P2: Dg16Config<ScalarField = E::ScalarField>,
+    P1::BaseField: FieldBytes,
+    P2::BaseField: FieldBytes,
+{
+    let (nc, ni) = (m.num_constraints, m.num_instance_variables);
+    let nv = ni + m.num_witness_variables;
+    let log_m = (nc + ni).next_power_of_two().trailing_zeros();
+    let domain = 1usize << log_m;
+    // alpha | beta | gamma | delta | tau, canonical little-endian (the caller owns the randomness)
+    let mut td = Vec::with_capacity(5 * 32);
+    for _ in 0..5 {
+        let mut x = E::ScalarField::rand(rng);
+        while x.is_zero() {
+            x = E::ScalarField::rand(rng);
+        }
+        td.extend(x.into_bigint().to_bytes_le());
+    }
+    let gens = {
+        let mut g = pack_affine(&[E::G1Affine::generator()]);
+        g.extend(pack_affine(&[E::G2Affine::generator()]));
+        g
+    };
+    let (ca, cb, cc) = (Csr::from_rows(&m.a), Csr::from_rows(&m.b), Csr::from_rows(&m.c));
+    let (f1, f2) = (2 * <P1::BaseField as FieldBytes>::BYTES, 2 * <P2::BaseField as FieldBytes>::BYTES);
+    let (mut a, mut b1, mut b2) = (vec![0u8; nv * f1], vec![0u8; nv * f1], vec![0u8; nv * f2]);
+    let (mut h, mut l) = (vec![0u8; domain * f1], vec![0u8; (nv - ni) * f1]);
+    let (mut fixed, mut gamma_g2, mut ic) = (vec![0u8; 3 * f1 + 2 * f2], vec![0u8; f2], vec![0u8; ni * f1]);
+    check(unsafe {
+        sys::dg16_groth16_setup(
+            CTX.0, P1::CURVE, nc, ni, nv, log_m,
+            ca.row_ptr.as_ptr(), ca.col.as_ptr(), scalars_as_bytes(&ca.coeff).as_ptr().cast(),
+            cb.row_ptr.as_ptr(), cb.col.as_ptr(), scalars_as_bytes(&cb.coeff).as_ptr().cast(),
+            cc.row_ptr.as_ptr(), cc.col.as_ptr(), scalars_as_bytes(&cc.coeff).as_ptr().cast(),
+            td.as_ptr().cast(), gens.as_ptr().cast(), a.as_mut_ptr().cast(), b1.as_mut_ptr().cast(),
+            b2.as_mut_ptr().cast(), h.as_mut_ptr().cast(), l.as_mut_ptr().cast(), fixed.as_mut_ptr().cast(),
+            gamma_g2.as_mut_ptr().cast(), ic.as_mut_ptr().cast(), 0,
+        )
+    })?;
+    let g1_fixed = unpack_affine::<P1>(&fixed[..3 * f1]);
+    let g2_fixed = unpack_affine::<P2>(&fixed[3 * f1..]);
+    let vk = VerifyingKey::<E> {
+        alpha_g1: g1_fixed[0],
+        beta_g2: g2_fixed[0],
+        gamma_g2: unpack_affine::<P2>(&gamma_g2)[0],
+        delta_g2: g2_fixed[1],
+        gamma_abc_g1: unpack_affine::<P1>(&ic),
+    };
+    Ok(ProvingKey::<E> {
+        vk,
+        beta_g1: g1_fixed[1],
+        delta_g1: g1_fixed[2],
+        a_query: unpack_affine::<P1>(&a),
+        b_g1_query: unpack_affine::<P1>(&b1),
+        b_g2_query: unpack_affine::<P2>(&b2),
+        h_query: unpack_affine::<P1>(&h),
+        l_query: unpack_affine::<P1>(&l),
+    })
+}

@@ -182,6 +182,19 @@ extern "C" {
                     b_out: *mut c_void, c_out: *mut c_void, flags: c_uint, channel: c_int) -> c_int;
     pub fn dg16_gen_bases(ctx: *mut Dg16Ctx, curve: c_int, group: c_int, seed: u64, n: usize, out: *mut c_void,
                           flags: c_uint, channel: c_int) -> c_int;
+    // key generation: fixed-base batch multiplication, Groth16 setup (circuit_specific_setup)
+    pub fn dg16_fixed_base_mul(ctx: *mut Dg16Ctx, curve: c_int, group: c_int, base: *const c_void,
+                               scalars: *const c_void, n: usize, out_affine: *mut c_void, flags: c_uint,
+                               channel: c_int) -> c_int;
+    pub fn dg16_fixed_base_window_bits(n: usize) -> c_uint;
+    pub fn dg16_groth16_setup(ctx: *mut Dg16Ctx, curve: c_int, num_constraints: usize, num_inputs: usize,
+                    num_vars: usize, log_m: c_uint, a_row_ptr: *const u32, a_col: *const u32,
+                    a_coeff: *const c_void, b_row_ptr: *const u32, b_col: *const u32, b_coeff: *const c_void,
+                    c_row_ptr: *const u32, c_col: *const u32, c_coeff: *const c_void, trapdoor: *const c_void,
+                    generators: *const c_void, a_query: *mut c_void, b_g1_query: *mut c_void,
+                    b_g2_query: *mut c_void, h_query: *mut c_void, l_query: *mut c_void,
+                    fixed_points: *mut c_void, gamma_g2: *mut c_void, gamma_abc_g1: *mut c_void,
+                    flags: c_uint) -> c_int;
     pub fn dg16_to_affine(ctx: *mut Dg16Ctx, curve: c_int, group: c_int, jac: *const c_void, out: *mut c_void,
                           n: usize, flags: c_uint, channel: c_int) -> c_int;
     // resident bases (a CRS is uploaded once; msm over its window tables)

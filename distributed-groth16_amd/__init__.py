@@ -17,3 +17,4 @@ from .lib import (  # noqa: F401
     F_DEVICE_PTRS,
     F_OUT_AFFINE,
 )
+from .keygen import generate_parameters, Parameters  # noqa: F401,E402

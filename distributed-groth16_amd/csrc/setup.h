@@ -1,0 +1,35 @@
+// Key generation (dg16_fixed_base_mul, dg16_groth16_setup): what setup.hip (C ABI, curve dispatch) needs from the
+// per-curve objects setup_<curve>.o (setup_curve.hip compiled once per curve id, the way prover_bn254.hip etc. are).
+#pragma once
+#include "ctx.h"
+
+namespace dg16 {
+
+struct SetupArgs {
+  size_t nc, ni, nv;
+  unsigned log_m;
+  const unsigned *row_ptr[3], *col[3];      // A, B, C as CSR by constraint (device pointers)
+  const void* coeff[3];                     // Montgomery form (device pointers)
+  size_t nnz[3];
+  const void* trapdoor;                     // host: alpha | beta | gamma | delta | tau, canonical
+  const void* generators;                   // host: g1 affine | g2 affine, or null
+  // device outputs
+  void *a_query, *b_g1_query, *b_g2_query, *h_query, *l_query, *fixed_points, *gamma_g2, *gamma_abc_g1;
+};
+
+// out_dev[i] = scalars_dev[i] * base (affine); base_host null = the standard generator
+template <int CURVE>
+void fixed_base_run(Call& k, int group, const void* base_host, const void* scalars_dev, size_t n, bool mont,
+                    void* out_dev);
+// the whole generator on the call's stream; synchronises before it returns (it owns temporary device memory)
+template <int CURVE>
+void groth16_setup_run(Call& k, const SetupArgs& a);
+// (defined in the per-curve objects)
+template <> void fixed_base_run<0>(Call&, int, const void*, const void*, size_t, bool, void*);
+template <> void fixed_base_run<1>(Call&, int, const void*, const void*, size_t, bool, void*);
+template <> void fixed_base_run<2>(Call&, int, const void*, const void*, size_t, bool, void*);
+template <> void groth16_setup_run<0>(Call&, const SetupArgs&);
+template <> void groth16_setup_run<1>(Call&, const SetupArgs&);
+template <> void groth16_setup_run<2>(Call&, const SetupArgs&);
+
+}  // namespace dg16

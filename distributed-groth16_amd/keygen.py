@@ -1,0 +1,173 @@
+"""Groth16 key generation on the GPU (`dg16_groth16_setup`, csrc/setup_curve.hip) -- the counterpart of
+`Groth16::<Bn254, CircomReduction>::circuit_specific_setup(circuit, rng)` as every program of the reference starts
+(groth16/examples/sha256.rs:137, million.rs:137, mpc-api/src/main.rs:151).
+
+    params = generate_parameters(ctx, "bn254", r1cs)          # R1CS of r1cs.py, or a dict of CSR arrays
+    pk = params.proving_key(ctx)                              # resident key (dg16_pk_create on device pointers)
+    ok = verify.verify_proof(*params.verifying_key(), public_inputs, proof_affine)
+
+The trapdoor (alpha, beta, gamma, delta, tau) is drawn from `secrets` unless the caller passes one; it is returned with
+the parameters only when it was passed in.  torch is the device-memory plumbing; there is no CPU path."""
+
+import secrets
+
+import numpy as np
+
+from . import lib as _lib
+
+FR_MODULUS = {
+    "bn254": 21888242871839275222246405745257275088548364400416034343698204186575808495617,
+    "bls12_381": 0x73EDA753299D7D483339D80809A1D80553BDA402FFFE5BFEFFFFFFFF00000001,
+    "bls12_377": 0x12AB655E9A2CA55660B44D1E5C37B00159AA76FED00000010A11800000000001,
+}
+TWO_ADICITY = {"bn254": 28, "bls12_381": 32, "bls12_377": 47}
+
+
+def draw_trapdoor(curve):
+    """Five uniform non-zero scalars (alpha, beta, gamma, delta, tau)."""
+    r = FR_MODULUS[curve]
+    return tuple(1 + secrets.randbelow(r - 1) for _ in range(5))
+
+
+def _trapdoor_array(curve, trapdoor):
+    r = FR_MODULUS[curve]
+    td = [int(x) for x in trapdoor]
+    if len(td) != 5:
+        raise ValueError("trapdoor = (alpha, beta, gamma, delta, tau)")
+    if any(not 0 < x < r for x in td):
+        raise ValueError("every trapdoor element must be non-zero and below r")
+    return np.array([[(x >> (64 * j)) & (2**64 - 1) for j in range(4)] for x in td], dtype=np.uint64)
+
+
+def _is_tensor(x):
+    return hasattr(x, "data_ptr")
+
+
+def _check_csr(name, csr, nc, nv):
+    ptr, col, coeff = csr
+    if any(_is_tensor(x) for x in csr):
+        if not all(_is_tensor(x) for x in csr):
+            raise ValueError("matrix %s mixes device tensors and host arrays" % name)
+        if ptr.numel() != nc + 1:
+            raise ValueError("matrix %s: row_ptr must have num_constraints + 1 entries" % name)
+        return csr            # indices on the device are checked by the library (DG16_ERR_BAD_ARG)
+    ptr = np.ascontiguousarray(ptr, dtype=np.uint32)
+    col = np.ascontiguousarray(col, dtype=np.uint32)
+    coeff = np.ascontiguousarray(coeff, dtype=np.uint64).reshape(-1, 4)
+    if ptr.shape != (nc + 1,):
+        raise ValueError("matrix %s: row_ptr must have num_constraints + 1 entries" % name)
+    if nc and (ptr[0] != 0 or np.any(ptr[1:] < ptr[:-1])):
+        raise ValueError("matrix %s: row_ptr must start at 0 and not decrease" % name)
+    nnz = int(ptr[-1]) if nc else 0
+    if col.shape[0] != nnz or coeff.shape[0] != nnz:
+        raise ValueError("matrix %s: col / coeff length differs from row_ptr[-1]" % name)
+    if nnz and int(col.max()) >= nv:
+        raise ValueError("matrix %s: column index >= num_vars" % name)
+    return ptr, col, coeff
+
+
+def prepare(curve, r1cs, trapdoor=None):
+    """Host-side argument handling of generate_parameters (no GPU involved): shapes of the constraint system, CSR
+    validation, the trapdoor.  r1cs: an `r1cs.R1CS` (canonical coefficients) or a dict with num_constraints,
+    num_inputs (incl. the constant 1), num_vars, a / b / c = (row_ptr, col, coeff) and coeff_mont (default True:
+    coefficients already in Montgomery form, the layout dg16_qap takes).
+    -> dict(nc, ni, nv, log_m, csr=[a, b, c], coeff_mont, trapdoor=uint64 [5][4], trapdoor_given)."""
+    if curve not in FR_MODULUS:
+        raise ValueError("unknown curve %r" % (curve,))
+    if isinstance(r1cs, dict):
+        nc, ni, nv = int(r1cs["num_constraints"]), int(r1cs["num_inputs"]), int(r1cs["num_vars"])
+        csr = [r1cs["a"], r1cs["b"], r1cs["c"]]
+        coeff_mont = bool(r1cs.get("coeff_mont", True))
+    else:
+        nc, ni, nv = int(r1cs.n_constraints), int(r1cs.num_inputs), int(r1cs.num_variables)
+        csr = list(r1cs.csr)
+        coeff_mont = False
+    if not (1 <= ni <= nv) or nc < 0:
+        raise ValueError("need 1 <= num_inputs <= num_vars")
+    log_m = max(nc + ni - 1, 0).bit_length()          # D::new(num_constraints + num_inputs).size()
+    if log_m + 1 > TWO_ADICITY[curve] or log_m > 26:
+        raise ValueError("domain larger than the field's 2-adic subgroup")
+    csr = [_check_csr(n, m, nc, nv) for n, m in zip("abc", csr)]
+    given = trapdoor is not None
+    td = _trapdoor_array(curve, trapdoor if given else draw_trapdoor(curve))
+    return dict(nc=nc, ni=ni, nv=nv, log_m=log_m, csr=csr, coeff_mont=coeff_mont, trapdoor=td, trapdoor_given=given)
+
+
+class Parameters:
+    """The generated key as device arrays (torch uint8 tensors, affine points, identity = zero bytes):
+    a_query, b_g1_query, b_g2_query, h_query, l_query, fixed_points (alpha_g1 | beta_g1 | delta_g1 | beta_g2 |
+    delta_g2), gamma_g2, gamma_abc_g1."""
+
+    NAMES = ("a_query", "b_g1_query", "b_g2_query", "h_query", "l_query", "fixed_points", "gamma_g2", "gamma_abc_g1")
+
+    def __init__(self, curve, nc, ni, nv, log_m, arrays, trapdoor=None):
+        self.curve, self.num_constraints, self.num_inputs, self.num_vars = curve, nc, ni, nv
+        self.log_m, self.domain_size = log_m, 1 << log_m
+        self.trapdoor = trapdoor
+        for n, t in zip(self.NAMES, arrays):
+            setattr(self, n, t)
+
+    def proving_key(self, ctx, shard=0, n_shards=1, h_cyclic=False):
+        """Resident proving key over the device arrays (no host round trip)."""
+        return ctx.pk_create(self.curve, self.num_vars, self.num_inputs, self.domain_size, self.a_query.data_ptr(),
+                             self.b_g1_query.data_ptr(), self.b_g2_query.data_ptr(), self.h_query.data_ptr(),
+                             self.l_query.data_ptr(), self.fixed_points.data_ptr(), device_ptrs=True, shard=shard,
+                             n_shards=n_shards, h_cyclic=h_cyclic)
+
+    def host(self, name):
+        """One array as numpy uint64 [points][limbs]."""
+        fq = _lib.FQ_LIMBS64[self.curve]
+        cols = {"b_g2_query": 4 * fq, "gamma_g2": 4 * fq, "fixed_points": fq}.get(name, 2 * fq)
+        return getattr(self, name).cpu().numpy().view(np.uint64).reshape(-1, cols)
+
+    def verifying_key(self):
+        """(alpha_g1, beta_g2, gamma_g2, delta_g2, ic): the first five arguments of verify.verify_proof."""
+        fq = _lib.FQ_LIMBS64[self.curve]
+        f = self.host("fixed_points").reshape(-1)
+        g2 = f[6 * fq:]
+        return f[:2 * fq].copy(), g2[:4 * fq].copy(), self.host("gamma_g2").reshape(-1), g2[4 * fq:].copy(), \
+            self.host("gamma_abc_g1")
+
+
+def generate_parameters(ctx, curve, r1cs, trapdoor=None, generators=None):
+    """ctx: a Context (None: one is made on device 0 -- without a GPU that raises Dg16Error, there is no CPU path).
+    generators: None, or (g1 affine, g2 affine) as uint64 arrays.  Returns Parameters."""
+    p = prepare(curve, r1cs, trapdoor)
+    if ctx is None:
+        ctx = _lib.Context(0)
+    import torch
+    dev = torch.device("cuda", ctx.device)
+    nc, ni, nv, log_m = p["nc"], p["ni"], p["nv"], p["log_m"]
+
+    def up(x, dtype):
+        if _is_tensor(x):
+            return x
+        x = np.ascontiguousarray(x, dtype=dtype)
+        if x.size == 0:
+            return torch.zeros(16, dtype=torch.uint8, device=dev)
+        return torch.from_numpy(x.view(np.uint8).reshape(-1)).to(dev)
+
+    mats = []
+    for ptr, col, coeff in p["csr"]:
+        d = (up(ptr, np.uint32), up(col, np.uint32), up(coeff, np.uint64))
+        if not p["coeff_mont"]:
+            nnz = d[2].numel() * d[2].element_size() // 32
+            if _is_tensor(coeff):
+                d = (d[0], d[1], d[2].clone())
+            torch.cuda.synchronize(dev)
+            ctx.field_op_dev(curve, "fr", 5, d[2].data_ptr(), None, d[2].data_ptr(), nnz)      # to Montgomery form
+        mats.append(d)
+    fqb = 8 * _lib.FQ_LIMBS64[curve]
+    g1b, g2b = 2 * fqb, 4 * fqb
+    sizes = (nv * g1b, nv * g1b, nv * g2b, (1 << log_m) * g1b, (nv - ni) * g1b, 3 * g1b + 2 * g2b, g2b, ni * g1b)
+    arrays = [torch.empty(max(s, 16), dtype=torch.uint8, device=dev)[:s] for s in sizes]
+    gens = None
+    if generators is not None:
+        gens = np.concatenate([np.ascontiguousarray(g, dtype=np.uint64).reshape(-1) for g in generators])
+        if gens.size * 8 != g1b + g2b:
+            raise ValueError("generators = (g1 affine, g2 affine)")
+    torch.cuda.synchronize(dev)        # the uploads ran on torch's stream, the generator runs on the library's
+    ctx.sync(0)
+    ctx.groth16_setup(curve, nc, ni, nv, log_m, *[[t.data_ptr() for t in m] for m in mats], p["trapdoor"],
+                      [t.data_ptr() for t in arrays], generators=gens, device_ptrs=True)
+    return Parameters(curve, nc, ni, nv, log_m, arrays, trapdoor=tuple(trapdoor) if p["trapdoor_given"] else None)

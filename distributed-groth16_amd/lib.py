@@ -136,6 +136,10 @@ def load():
     L.dg16_h_poly.argtypes = [vp, i, vp, vp, vp, u, vp, u, i]
     L.dg16_msm.argtypes = [vp, i, i, vp, vp, sz, sz, u, i, vp]
     L.dg16_gen_bases.argtypes = [vp, i, i, u64, sz, vp, u, i]
+    L.dg16_fixed_base_mul.argtypes = [vp, i, i, vp, vp, sz, vp, u, i]
+    L.dg16_fixed_base_window_bits.argtypes = [sz]
+    L.dg16_fixed_base_window_bits.restype = u
+    L.dg16_groth16_setup.argtypes = [vp, i, sz, sz, sz, u] + [vp] * 19 + [u]
     if hasattr(L, "dg16_ctx_set_table_budget"):      # (absent from older builds named by DG16_LIB for A/B timing)
         L.dg16_ctx_set_table_budget.argtypes = [vp, u64]
     L.dg16_bases_upload.argtypes = [vp, i, i, vp, sz, u, ctypes.POINTER(vp)]
@@ -252,7 +256,7 @@ EXPORTED = ["dg16_ctx_create", "dg16_ctx_destroy", "dg16_last_error", "dg16_set_
             "dg16_r1cs_free", "dg16_zkey_parse", "dg16_zkey_header_get", "dg16_zkey_points", "dg16_zkey_matrix",
             "dg16_zkey_free", "dg16_serialize_error", "dg16_proof_compress", "dg16_proof_decompress",
             "dg16_verify_error", "dg16_groth16_verify", "dg16_prove_a", "dg16_prove_b", "dg16_prove_c",
-            "dg16_ctx_set_table_budget"]
+            "dg16_ctx_set_table_budget", "dg16_fixed_base_mul", "dg16_fixed_base_window_bits", "dg16_groth16_setup"]
 
 
 def _ptr(x):
@@ -488,6 +492,40 @@ class Context:
         out = np.zeros((n, nl), dtype=np.uint64)
         self._chk(self.L.dg16_gen_bases(self.h, CURVES[curve], group, seed, n, _ptr(out), 0, channel))
         return out
+
+    def fixed_base_mul(self, curve, group, scalars, base=None, scalars_mont=False, channel=0):
+        """out[i] = scalars[i] * base (affine, identity = zeros).  scalars: uint64 [n][4]; base: one affine point as a
+        uint64 array, or None for the curve's standard generator."""
+        scalars = np.ascontiguousarray(scalars, dtype=np.uint64).reshape(-1, 4)
+        base = None if base is None else np.ascontiguousarray(base, dtype=np.uint64)
+        nl = FQ_LIMBS64[curve] * 2 * (2 if group == 2 else 1)
+        out = np.zeros((scalars.shape[0], nl), dtype=np.uint64)
+        self._chk(self.L.dg16_fixed_base_mul(self.h, CURVES[curve], group, _ptr(base), _ptr(scalars), scalars.shape[0],
+                                             _ptr(out), F_SCALARS_MONT if scalars_mont else 0, channel))
+        return out
+
+    def fixed_base_mul_dev(self, curve, group, scalars_ptr, n, out_ptr, base=None, scalars_mont=False, channel=0):
+        """Device pointers for the scalars and the output (stream-ordered on the channel); base stays a host array."""
+        base = None if base is None else np.ascontiguousarray(base, dtype=np.uint64)
+        self._chk(self.L.dg16_fixed_base_mul(self.h, CURVES[curve], group, _ptr(base), _ptr(scalars_ptr), n,
+                                             _ptr(out_ptr), F_DEVICE_PTRS | (F_SCALARS_MONT if scalars_mont else 0),
+                                             channel))
+
+    def groth16_setup(self, curve, num_constraints, num_inputs, num_vars, log_m, csr_a, csr_b, csr_c, trapdoor,
+                      outputs, generators=None, device_ptrs=False):
+        """dg16_groth16_setup.  csr_* = (row_ptr, col, coeff): numpy arrays (coeff uint64 [nnz][4], Montgomery form) or
+        raw device pointers with device_ptrs; trapdoor: uint64 [5][4] canonical (host); generators: host array g1 | g2 or
+        None; outputs: the eight arrays / device pointers a_query, b_g1_query, b_g2_query, h_query, l_query,
+        fixed_points, gamma_g2, gamma_abc_g1.  Synchronous."""
+        trapdoor = np.ascontiguousarray(trapdoor, dtype=np.uint64)
+        generators = None if generators is None else np.ascontiguousarray(generators, dtype=np.uint64)
+        mats = []
+        for m in (csr_a, csr_b, csr_c):
+            mats += list(m) if device_ptrs else [np.ascontiguousarray(x) for x in m]
+        keep = (trapdoor, generators, mats)          # noqa: F841 (the arrays outlive the call)
+        self._chk(self.L.dg16_groth16_setup(self.h, CURVES[curve], num_constraints, num_inputs, num_vars, log_m,
+                                            *[_ptr(x) for x in mats], _ptr(trapdoor), _ptr(generators),
+                                            *[_ptr(x) for x in outputs], F_DEVICE_PTRS if device_ptrs else 0))
 
     def to_affine(self, curve, group, jac, channel=0):
         jac = np.ascontiguousarray(jac, dtype=np.uint64)

@@ -13,6 +13,8 @@
  *   dg16_qap            <- `qap::qap` (R1CS x witness)          groth16/src/qap.rs:44-91
  *   dg16_field_op       <- element-wise ark-ff ops (parity probe for the Montgomery kernels)
  *   dg16_gen_bases      <- `PackedProvingKeyShare::rand`       groth16/src/proving_key.rs:112-155
+ *   dg16_groth16_setup  <- `circuit_specific_setup`             groth16/examples/sha256.rs:137
+ *                          (dg16_fixed_base_mul <- FixedBase::msm inside it)
  *   dg16_groth16_prove  <- `create_proof_with_reduction_and_matrices`  groth16/examples/sha256.rs:159
  *                          and the A/B/C assembly of groth16/src/prove.rs:21-136
  *
@@ -172,6 +174,40 @@ int dg16_gen_bases(dg16_ctx *ctx, int curve, int group, uint64_t seed, size_t n,
 /* Jacobian -> affine for n points (n inversions on the device, one thread each). */
 int dg16_to_affine(dg16_ctx *ctx, int curve, int group, const void *jac, void *out, size_t n,
                    unsigned flags, int channel);
+
+/* ---- key generation: fixed-base batch multiplication and the Groth16 generator --------------------------------
+ * out[i] = scalars[i] * base as affine points (identity = all-zero bytes).  base: one affine point of `group` (HOST
+ * pointer even with DG16_F_DEVICE_PTRS; NULL = the curve's standard generator).  Replaces FixedBase::get_window_table +
+ * FixedBase::msm of ark-groth16's generator (generate_parameters_with_qap, reached from circuit_specific_setup:
+ * groth16/examples/sha256.rs:137, million.rs:137, mpc-api/src/main.rs:151).  Scalars: canonical integers below r, or
+ * Montgomery form with DG16_F_SCALARS_MONT.  A table of signed window multiples of the base is built on the device per
+ * call; its window width depends on n alone (dg16_fixed_base_window_bits: floor(log2 n) - 3 clamped to 4..16), and a
+ * point costs ceil((scalar bits + 1) / width) mixed additions and no doublings.  n = 0 is a no-op. */
+int dg16_fixed_base_mul(dg16_ctx *ctx, int curve, int group, const void *base, const void *scalars, size_t n,
+                        void *out_affine, unsigned flags, int channel);
+unsigned dg16_fixed_base_window_bits(size_t n);
+
+/* Groth16 parameters for an R1CS, CircomReduction flavour: replaces generate_parameters_with_qap as reached from
+ * `Groth16::<Bn254, CircomReduction>::circuit_specific_setup` (groth16/examples/sha256.rs:137, d_sha256.rs:138,
+ * test.rs:147,160, groth16/src/qap.rs:234, proving_key.rs:186) -- LibsnarkReduction::instance_map_with_evaluation
+ * (through ark-circom/src/circom/qap.rs:20-25) and CircomReduction::h_query_scalars (qap.rs:94-110) -- all on the device.
+ * A, B, C: CSR by constraint, coefficients in Montgomery form (the layout dg16_qap takes; C as well here).  trapdoor:
+ * HOST pointer to alpha | beta | gamma | delta | tau (5 x 32 bytes, canonical, all non-zero and below r; tau^m != 1,
+ * m = 2^log_m = D::new(num_constraints + num_inputs).size()), else DG16_ERR_BAD_ARG: the caller owns the randomness.
+ * generators: HOST pointer to g1 affine | g2 affine, or NULL for the standard generators.  Outputs (device pointers
+ * iff DG16_F_DEVICE_PTRS, like the matrices), affine, identity = zero bytes:
+ *   a_query, b_g1_query [num_vars] G1 | b_g2_query [num_vars] G2 | h_query [2^log_m] G1 |
+ *   l_query [num_vars - num_inputs] G1 | fixed_points = alpha_g1 | beta_g1 | delta_g1 | beta_g2 | delta_g2 (the
+ *   dg16_pk_create layout) | gamma_g2 (one G2) | gamma_abc_g1 [num_inputs] G1.
+ * Synchronous in both forms (it owns temporary device memory); runs on channel 0.  A matrix entry whose column is
+ * not a wire, or a row_ptr that is not ordered, is DG16_ERR_BAD_ARG. */
+int dg16_groth16_setup(dg16_ctx *ctx, int curve, size_t num_constraints, size_t num_inputs, size_t num_vars,
+                       unsigned log_m, const uint32_t *a_row_ptr, const uint32_t *a_col, const void *a_coeff,
+                       const uint32_t *b_row_ptr, const uint32_t *b_col, const void *b_coeff,
+                       const uint32_t *c_row_ptr, const uint32_t *c_col, const void *c_coeff,
+                       const void *trapdoor, const void *generators, void *a_query, void *b_g1_query,
+                       void *b_g2_query, void *h_query, void *l_query, void *fixed_points, void *gamma_g2,
+                       void *gamma_abc_g1, unsigned flags);
 
 /* ---- Groth16 prover (single prover; the value the n-party run must equal) ------------------------
  * Replaces `Groth16::<E, CircomReduction>::create_proof_with_reduction_and_matrices` (third-party
