@@ -10,6 +10,7 @@
 //! | [`ntt`]     | `domain.fft_in_place` / `ifft_in_place`, the NTT part of `witness_map_from_matrices`  ark-circom/src/circom/qap.rs:64-91 | `dg16_ntt`, `dg16_h_poly` |
 //! | [`prove`]   | `create_proof_with_reduction_and_matrices`  groth16/examples/sha256.rs:159, `qap::qap`  groth16/src/qap.rs:44-91 | `dg16_pk_create`, `dg16_qap`, `dg16_groth16_prove` |
 //! | [`setup`]   | `Groth16::<E, CircomReduction>::circuit_specific_setup`  groth16/examples/sha256.rs:137 | `dg16_groth16_setup` |
+//! | [`verify`]  | `Groth16::<E>::verify_proof` per proof  groth16/examples/sha256.rs:228-254, mpc-api verify endpoint | `dg16_vk_create`, `dg16_groth16_verify_batch` |
 //! | [`net`]     | `MpcNet` / `MpcSerNet` (mpc-net/src/lib.rs:46-140, dist-primitives/src/channel/mod.rs:7-60) and the packed-secret-sharing primitives over it | `dg16_net` vtable, `dg16_rccl_*`, `dg16_d_*`, `dg16_prove_a/_b/_c` |
 //!
 //! Memory layout: `ark_ec::short_weierstrass::Affine<P>` is `{x, y, infinity: bool}` with Rust's default (unspecified)
@@ -23,6 +24,7 @@ pub mod ntt;
 pub mod pack;
 pub mod prove;
 pub mod setup;
+pub mod verify;
 
 use dg16_sys as sys;
 use once_cell::sync::Lazy;

@@ -1,0 +1,82 @@
+//! Batched verification: `Groth16::<E>::verify_proof(&pvk, &proof, &inputs)` for many proofs of one key in ONE call of
+//! `dg16_groth16_verify_batch` (the reference verifies after every proof: groth16/examples/sha256.rs:228-254, the verify
+//! endpoint of mpc-api/src/main.rs).  `PreparedVk::new` is `prepare_verifying_key`: it validates the key and builds its
+//! Miller-loop tables once.  BN254 and BLS12-381.
+//!
+//! Like the rest of this crate: never compiled here (bindings/README.md) -- source for a maintainer's box with cargo.
+use crate::pack::{pack_affine, scalars_as_bytes, FieldBytes};
+use crate::{check, sys, Dg16Config, Dg16Error, CTX};
+use ark_ec::pairing::Pairing;
+use ark_ec::short_weierstrass::Affine;
+use ark_groth16::{Proof, VerifyingKey};
+
+pub struct PreparedVk {
+    h: *mut sys::Dg16Vk,
+    n_public: usize,
+}
+unsafe impl Send for PreparedVk {}
+unsafe impl Sync for PreparedVk {}
+impl Drop for PreparedVk {
+    fn drop(&mut self) {
+        unsafe { sys::dg16_vk_destroy(self.h) }
+    }
+}
+
+impl PreparedVk {
+    pub fn new<E, P1, P2>(vk: &VerifyingKey<E>) -> Result<Self, Dg16Error>
+    where
+        E: Pairing<G1Affine = Affine<P1>, G2Affine = Affine<P2>>,
+        P1: Dg16Config<ScalarField = E::ScalarField>,
+        P2: Dg16Config<ScalarField = E::ScalarField>,
+        P1::BaseField: FieldBytes,
+        P2::BaseField: FieldBytes,
+    {
+        let (alpha, ic) = (pack_affine(&[vk.alpha_g1]), pack_affine(&vk.gamma_abc_g1));
+        let (beta, gamma, delta) = (pack_affine(&[vk.beta_g2]), pack_affine(&[vk.gamma_g2]), pack_affine(&[vk.delta_g2]));
+        let mut h = core::ptr::null_mut();
+        check(unsafe {
+            sys::dg16_vk_create(
+                CTX.0, P1::CURVE, alpha.as_ptr().cast(), beta.as_ptr().cast(), gamma.as_ptr().cast(),
+                delta.as_ptr().cast(), ic.as_ptr().cast(), vk.gamma_abc_g1.len(), 0, &mut h,
+            )
+        })?;
+        Ok(PreparedVk { h, n_public: vk.gamma_abc_g1.len() - 1 })
+    }
+}
+
+/// One verdict per proof; `inputs[i]` are proof i's public inputs (without the constant 1).  A malformed proof or input
+/// is `false` for that proof, never an error of the call.
+pub fn verify_batch<E, P1, P2>(pvk: &PreparedVk, inputs: &[Vec<E::ScalarField>], proofs: &[Proof<E>])
+    -> Result<Vec<bool>, Dg16Error>
+where
+    E: Pairing<G1Affine = Affine<P1>, G2Affine = Affine<P2>>,
+    P1: Dg16Config<ScalarField = E::ScalarField>,
+    P2: Dg16Config<ScalarField = E::ScalarField>,
+    P1::BaseField: FieldBytes,
+    P2::BaseField: FieldBytes,
+{
+    if inputs.len() != proofs.len() {
+        return Err(Dg16Error::LengthMismatch(inputs.len().min(proofs.len())));
+    }
+    let mut x = Vec::with_capacity(proofs.len() * pvk.n_public * 32);
+    for row in inputs {
+        if row.len() != pvk.n_public {
+            return Err(Dg16Error::LengthMismatch(row.len().min(pvk.n_public)));
+        }
+        x.extend_from_slice(scalars_as_bytes(row));
+    }
+    let mut p = Vec::new();
+    for pr in proofs {
+        p.extend(pack_affine(&[pr.a]));
+        p.extend(pack_affine(&[pr.b]));
+        p.extend(pack_affine(&[pr.c]));
+    }
+    let mut verdict = vec![0u8; proofs.len()];
+    check(unsafe {
+        sys::dg16_groth16_verify_batch(
+            CTX.0, pvk.h, x.as_ptr().cast(), pvk.n_public, p.as_ptr().cast(), proofs.len(),
+            sys::DG16_F_SCALARS_MONT, verdict.as_mut_ptr(), 0,
+        )
+    })?;
+    Ok(verdict.into_iter().map(|v| v == 1).collect())
+}

@@ -11,7 +11,7 @@ use std::os::raw::{c_char, c_int, c_uint, c_void};
 macro_rules! opaque {
     ($($name:ident),*) => { $(#[repr(C)] pub struct $name { _p: [u8; 0], _m: core::marker::PhantomData<(*mut u8, core::marker::PhantomPinned)> })* };
 }
-opaque!(Dg16Ctx, Dg16Pk, Dg16Bases, Dg16Pss, Dg16LocalNet, Dg16Rccl, Dg16R1cs, Dg16Zkey);
+opaque!(Dg16Ctx, Dg16Pk, Dg16Bases, Dg16Pss, Dg16LocalNet, Dg16Rccl, Dg16R1cs, Dg16Zkey, Dg16Vk);
 
 // enum dg16_curve
 pub const DG16_BN254: c_int = 0;
@@ -289,6 +289,14 @@ extern "C" {
     pub fn dg16_groth16_verify(curve: c_int, alpha_g1: *const c_void, beta_g2: *const c_void, gamma_g2: *const c_void,
                                delta_g2: *const c_void, ic: *const c_void, n_ic: usize, public_inputs: *const c_void,
                                n_public: usize, proof_affine: *const c_void, flags: c_uint, accepted: *mut c_int) -> c_int;
+    // batched verification on the GPU (BN254, BLS12-381): a prepared verifying key and one call per batch
+    pub fn dg16_vk_create(ctx: *mut Dg16Ctx, curve: c_int, alpha_g1: *const c_void, beta_g2: *const c_void,
+                          gamma_g2: *const c_void, delta_g2: *const c_void, ic: *const c_void, n_ic: usize,
+                          flags: c_uint, out: *mut *mut Dg16Vk) -> c_int;
+    pub fn dg16_vk_destroy(vk: *mut Dg16Vk);
+    pub fn dg16_groth16_verify_batch(ctx: *mut Dg16Ctx, vk: *const Dg16Vk, public_inputs: *const c_void,
+                                     n_public: usize, proofs_affine: *const c_void, n_proofs: usize, flags: c_uint,
+                                     verdict: *mut u8, channel: c_int) -> c_int;
     // ---- dist-primitives over an MpcNet (packed secret sharing): d_fft, d_msm, d_pp, deg_red, ext_wit::h, prove::A/B/C ----
     pub fn dg16_pss_create(ctx: *mut Dg16Ctx, curve: c_int, l: c_uint, out: *mut *mut Dg16Pss) -> c_int;
     pub fn dg16_d_fft(ctx: *mut Dg16Ctx, pp: *const Dg16Pss, net: *const Dg16Net, share: *const c_void,

@@ -18,3 +18,4 @@ from .lib import (  # noqa: F401
     F_OUT_AFFINE,
 )
 from .keygen import generate_parameters, Parameters  # noqa: F401,E402
+from .verify import PreparedVerifyingKey  # noqa: F401,E402

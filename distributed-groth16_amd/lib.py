@@ -234,6 +234,10 @@ def load():
     L.dg16_verify_error.argtypes = []
     L.dg16_verify_error.restype = ctypes.c_char_p
     L.dg16_groth16_verify.argtypes = [i, vp, vp, vp, vp, vp, sz, vp, sz, vp, u, ctypes.POINTER(i)]
+    L.dg16_vk_create.argtypes = [vp, i, vp, vp, vp, vp, vp, sz, u, ctypes.POINTER(vp)]
+    L.dg16_vk_destroy.argtypes = [vp]
+    L.dg16_vk_destroy.restype = None
+    L.dg16_groth16_verify_batch.argtypes = [vp, vp, vp, sz, vp, sz, u, vp, i]
     _lib = L
     return L
 
@@ -256,7 +260,8 @@ EXPORTED = ["dg16_ctx_create", "dg16_ctx_destroy", "dg16_last_error", "dg16_set_
             "dg16_r1cs_free", "dg16_zkey_parse", "dg16_zkey_header_get", "dg16_zkey_points", "dg16_zkey_matrix",
             "dg16_zkey_free", "dg16_serialize_error", "dg16_proof_compress", "dg16_proof_decompress",
             "dg16_verify_error", "dg16_groth16_verify", "dg16_prove_a", "dg16_prove_b", "dg16_prove_c",
-            "dg16_ctx_set_table_budget", "dg16_fixed_base_mul", "dg16_fixed_base_window_bits", "dg16_groth16_setup"]
+            "dg16_ctx_set_table_budget", "dg16_fixed_base_mul", "dg16_fixed_base_window_bits", "dg16_groth16_setup",
+            "dg16_vk_create", "dg16_vk_destroy", "dg16_groth16_verify_batch"]
 
 
 def _ptr(x):

@@ -1,7 +1,9 @@
-"""Groth16 verification (BN254) through libdg16's native verifier (`dg16_groth16_verify`, csrc/verify.hip) -- the
-counterpart of `Groth16::<Bn254>::verify_proof` as the reference calls it (groth16/examples/sha256.rs:228-254, the
-verify endpoint of mpc-api/src/main.rs, zk-cli verify).  Points are affine x || y Montgomery limbs (uint64), the
-layout of a zkey's header / IC section and of `serialize.decompress_to_limbs`."""
+"""Groth16 verification through libdg16 -- the counterpart of `Groth16::<E>::verify_proof` as the reference calls it
+(groth16/examples/sha256.rs:228-254, the verify endpoint of mpc-api/src/main.rs, zk-cli verify).  Two paths:
+`verify_proof` / `verify_with_zkey`: the host verifier (`dg16_groth16_verify`, csrc/verify.hip; BN254, one proof per
+call); `PreparedVerifyingKey`: batches on the GPU (`dg16_vk_create` + `dg16_groth16_verify_batch`; BN254 and
+BLS12-381).  Points are affine x || y Montgomery limbs (uint64), the layout of a zkey's header / IC section and of
+`serialize.decompress_to_limbs`."""
 
 import ctypes
 
@@ -34,3 +36,76 @@ def verify_with_zkey(zkey, public_inputs, proof_affine, scalars_mont=False):
     """Verification key taken from a parsed `.zkey` (zkey.ZKey): alpha, beta, gamma, delta and IC as they lie in it."""
     return verify_proof(zkey.alpha_g1, zkey.beta_g2, zkey.gamma_g2, zkey.delta_g2, zkey.ic, public_inputs,
                         proof_affine, scalars_mont=scalars_mont)
+
+
+class PreparedVerifyingKey:
+    """A verifying key validated and prepared once on `ctx`'s GPU (`ark_groth16::PreparedVerifyingKey`): the Miller value
+    of (alpha, beta) and the Miller-loop line tables of gamma and delta.  Raises Dg16Error(BAD_ARG) for a malformed key
+    (non-reduced coordinate, point off its curve or outside the order-r subgroup), UNSUPPORTED for BLS12-377."""
+
+    def __init__(self, ctx, curve, alpha_g1, beta_g2, gamma_g2, delta_g2, ic):
+        self.ctx, self.curve = ctx, curve
+        self.fq = _lib.FQ_LIMBS64[curve]
+        arr = lambda x: np.ascontiguousarray(x, dtype=np.uint64)
+        alpha_g1, beta_g2, gamma_g2, delta_g2 = (arr(x).reshape(-1) for x in (alpha_g1, beta_g2, gamma_g2, delta_g2))
+        ic = arr(ic).reshape(-1, 2 * self.fq)
+        if alpha_g1.size != 2 * self.fq or any(x.size != 4 * self.fq for x in (beta_g2, gamma_g2, delta_g2)):
+            raise ValueError("verifying key points have the wrong size for %s" % curve)
+        self.n_public = ic.shape[0] - 1
+        p = lambda x: x.ctypes.data_as(ctypes.c_void_p)
+        h = ctypes.c_void_p()
+        ctx._chk(ctx.L.dg16_vk_create(ctx.h, _lib.CURVES[curve], p(alpha_g1), p(beta_g2), p(gamma_g2), p(delta_g2),
+                                      p(ic), ic.shape[0], 0, ctypes.byref(h)))
+        self.h = h
+
+    @classmethod
+    def from_zkey(cls, ctx, zkey):
+        """Key material as it lies in a parsed `.zkey` (zkey.ZKey; BN254)."""
+        return cls(ctx, "bn254", zkey.alpha_g1, zkey.beta_g2, zkey.gamma_g2, zkey.delta_g2, zkey.ic)
+
+    @classmethod
+    def from_parameters(cls, ctx, params):
+        """The verifying key of a `keygen.generate_parameters` result."""
+        return cls(ctx, params.curve, *params.verifying_key())
+
+    def verify_batch(self, public_inputs, proofs, scalars_mont=False, device=False, channel=0, n_proofs=None):
+        """public_inputs: n_proofs x n_public scalars (4 uint64 each); proofs: n_proofs x (A | B | C) affine
+        (8 field elements each).  Returns one bool per proof.  device=True: both are raw device pointers (ints) or
+        objects with data_ptr(), n_proofs is required, and the verdicts are read back after the channel has drained."""
+        flags = _lib.F_SCALARS_MONT if scalars_mont else 0
+        L, ctx = self.ctx.L, self.ctx
+        if device:
+            import torch
+            ptr = lambda x: x.data_ptr() if hasattr(x, "data_ptr") else int(x or 0)
+            if n_proofs is None:
+                raise ValueError("n_proofs is required with device pointers")
+            out = torch.zeros(max(n_proofs, 1), dtype=torch.uint8, device="cuda:%d" % self.ctx.device)
+            ctx._chk(L.dg16_groth16_verify_batch(ctx.h, self.h, ctypes.c_void_p(ptr(public_inputs)), self.n_public,
+                                                 ctypes.c_void_p(ptr(proofs)), n_proofs, flags | _lib.F_DEVICE_PTRS,
+                                                 ctypes.c_void_p(out.data_ptr()), channel))
+            ctx.sync(channel)
+            return out[:n_proofs].cpu().numpy().astype(bool)
+        proofs = np.ascontiguousarray(proofs, dtype=np.uint64).reshape(-1, 8 * self.fq)
+        n = proofs.shape[0]
+        pub = np.ascontiguousarray(public_inputs, dtype=np.uint64)
+        if n == 0:
+            n_public = self.n_public
+        elif pub.size % (4 * n):
+            raise ValueError("public_inputs is not n_proofs x n_public scalars")
+        else:
+            n_public = pub.size // (4 * n)      # the library compares it with the key (LENGTH_MISMATCH)
+        out = np.zeros(max(n, 1), dtype=np.uint8)
+        p = lambda x: x.ctypes.data_as(ctypes.c_void_p)
+        ctx._chk(L.dg16_groth16_verify_batch(ctx.h, self.h, p(pub), n_public, p(proofs), n, flags, p(out), channel))
+        return out[:n].astype(bool)
+
+    def close(self):
+        if self.h:
+            self.ctx.L.dg16_vk_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass

@@ -574,6 +574,36 @@ int dg16_groth16_verify(int curve, const void *alpha_g1, const void *beta_g2, co
                         const void *delta_g2, const void *ic, size_t n_ic, const void *public_inputs,
                         size_t n_public, const void *proof_affine, unsigned flags, int *accepted);
 
+/* ---- Batched Groth16 verification on the GPU, BN254 and BLS12-381 -------------------------------------------------
+ *   dg16_vk_create             <- ark_groth16::prepare_verifying_key / PreparedVerifyingKey
+ *   dg16_groth16_verify_batch  <- Groth16::verify_proof / verify_proof_with_prepared_inputs, once per proof
+ * The equation and the point layout of dg16_groth16_verify above (affine x || y Montgomery limbs, identity = zeros;
+ * 32-byte Fq for BN254, 48-byte for BLS12-381), decided on the device by an optimal ate pairing, one proof per lane.
+ * DG16_BLS12_377 returns DG16_ERR_UNSUPPORTED from dg16_vk_create: the reference proves on BN254, and there is no
+ * independent BLS12-377 pairing to check a verifier against.
+ * dg16_vk_create validates the key by the rules above -- a non-reduced coordinate, a point off its curve, a G2 point
+ * outside the order-r subgroup: DG16_ERR_BAD_ARG; on BLS12-381 G1 has a cofactor, so alpha_g1 and every ic point are
+ * subgroup-checked too -- and does the per-key work once: the Miller value of (alpha, beta) and the Miller-loop line
+ * tables of gamma and delta.  The key's pointers are host pointers, or all device pointers with DG16_F_DEVICE_PTRS
+ * (no other flag is accepted); the call is synchronous and the handle owns its device memory until dg16_vk_destroy.
+ * dg16_groth16_verify_batch: public_inputs = n_proofs x n_public scalars (row i belongs to proof i), proofs_affine =
+ * n_proofs x (A | B | C), verdict = n_proofs bytes.  verdict[i] = 1 iff proof i passes every check and the equation
+ * holds, else 0.  n_public + 1 != n_ic returns DG16_ERR_LENGTH_MISMATCH; n_proofs = 0 is DG16_OK.  Whatever is wrong
+ * with ONE proof rejects THAT proof and nothing else: a non-reduced proof coordinate, a proof point off its curve, B
+ * outside the subgroup, on BLS12-381 also A or C outside the subgroup, and a public input >= r (the single-proof call
+ * returns DG16_ERR_BAD_ARG for that; here x and x + r are still not the same input, but one sender's bad input does
+ * not fail the batch).  Identity points in a proof are legal: the verdict is what the equation gives.
+ * DG16_F_SCALARS_MONT as everywhere; host pointers: synchronous; DG16_F_DEVICE_PTRS: stream-ordered on `channel`,
+ * verdict a device pointer (16-byte aligned inputs and proofs).  Temporaries come from the channel's workspace
+ * (DG16_ERR_OOM leaves the context usable).  Per-proof verdicts only: no random-linear-combination batching. */
+typedef struct dg16_vk dg16_vk;
+int dg16_vk_create(dg16_ctx *ctx, int curve, const void *alpha_g1, const void *beta_g2, const void *gamma_g2,
+                   const void *delta_g2, const void *ic, size_t n_ic, unsigned flags, dg16_vk **out);
+void dg16_vk_destroy(dg16_vk *vk);
+int dg16_groth16_verify_batch(dg16_ctx *ctx, const dg16_vk *vk, const void *public_inputs, size_t n_public,
+                              const void *proofs_affine, size_t n_proofs, unsigned flags, uint8_t *verdict,
+                              int channel);
+
 /* Duration in milliseconds of the dominant kernel(s) of the most recent call on `channel`
  * (HIP events recorded on the channel's stream); 0 if none.  which: 0 = whole call,
  * 1 = bucket accumulation (MSM) / butterfly passes (NTT); 2 = NOT a duration: the shader clock in MHz the chip held
