@@ -272,7 +272,8 @@ static size_t msm_results_bytes() {
 // overlap_tail (DG16_F_OVERLAP_TAIL, one GPU): H's bucket reduction -- the exposed tail of a proof, ~0.6 ms of latency-bound
 // launches on an otherwise idle chip -- goes down channel 2's stream instead of channel 0's, so that what the caller
 // enqueues next on channel 0 (the next proof's R1CS x witness and h-polynomial) runs under it.  Returns true when it did:
-// H's result is then ordered on channel 2's stream, everything else on channel 0's as before.  The buffers the tail
+// H's result is then ordered on channel 2's stream; the other results on channel 0's as before, except in the queued form
+// below (one GPU, whole h-polynomial), where channel 2's stream alone is ordered behind all of them.  The buffers the tail
 // still reads when the next proof starts (H's buckets and digit-sort metadata, the results record) are fenced with
 // pipe_ev[18] at their first reuse (marked "tail fence" below); other entry points wait in Call().
 template <int CURVE>
@@ -310,14 +311,8 @@ static bool msms_typed(dg16_ctx* ctx, Call& k0, Call& k1, Call& k2, const PkDev&
   Jacobian<Fq>* res_h = rec + kRecH;
   Jacobian<Fq2>* res_b2 = (Jacobian<Fq2>*)(res_dev + kRecG1 * g1j);
   const int first_shard = pk.shard == 0;
-  DG_HIP(hipMemcpyAsync(r_s, r_s_host, 2 * sizeof(Fr), hipMemcpyHostToDevice, k0.s()));
   // ONE scalar vector for A, B1, B and L: w[1..] slice ++ [r, s, -rs]
   Fr* sc_ab = (Fr*)ws(k0.c, 23, (n_ab + 3) * sizeof(Fr));
-  DG_HIP(hipMemcpyAsync(sc_ab, w_dev + 1 + pk.ab_lo, n_ab * sizeof(Fr), hipMemcpyDeviceToDevice, k0.s()));
-  hipLaunchKernelGGL(prover_scalar_prep_kernel<Fr>, dim3(1), dim3(1), 0, k0.s(), r_s, sc_ab, n_ab, (int)mont,
-                     (int)(pk.shard + 1 == pk.nshards));
-  DG_HIP(hipGetLastError());
-  DG_HIP(hipEventRecord(ctx->pipe_ev[8], k0.s()));
   // Scheduling.  Every saturating kernel of a proof (bucket accumulations, NTTs) goes down ONE stream (channel 0):
   // they are all VALU-bound, and co-scheduling them was measured equal at best and up to 1.7x worse from run to run.
   // The latency-bound bucket reductions and the serial s*A, r*B1 run on channels 1 / 2 behind the next accumulation;
@@ -356,23 +351,70 @@ static bool msms_typed(dg16_ctx* ctx, Call& k0, Call& k1, Call& k2, const PkDev&
     DG_HIP(hipEventRecord(ev[ev_done], xch));
   };
 
+  // A queue of proofs (overlap_tail on one GPU, the whole h-polynomial): the main stream is NOT joined with the side streams
+  // at the end of a proof, so the next proof's R1CS x witness and h-polynomial start right behind H's accumulation instead
+  // of behind L's reduction (0.3 ms of idle main stream per 2^20 proof), and the prologue (r, s, the scalar vector) runs on
+  // `side` in front of the sort that consumes it.  What the last proof's side streams may still touch is fenced at its first
+  // reuse instead -- every buffer, who touches it last, the event behind that, and the next proof's first touch:
+  //   r_s (k0 slot 22)            read: stage 1 on xch            ev[7]    written: r, s copy on side      <- side waits ev[7]
+  //   sc_ab (k0 slot 23)          read: sort of w on side         in order written: w copy, prep on side   (in order)
+  //   st_ab (k1 slots 4-6, 9, 25) read: B's reduction on side2    ev[5]    written: sort of w on side      <- side waits ev[5]
+  //                               read: B1's reduction on xch     ev[7]                                    <- side waits ev[7]
+  //                               read: A's, L's reductions (side), the accumulations (main)              in order / ev[8]
+  //   buf_b2 (k2 slots 7-17)      read: B's reduction on side2    ev[5]    written: B's accumulation (main) <- main waits ev[13],
+  //                                                                         recorded on side behind the wait for ev[5]
+  //   buf_b1 (k1 slots 7-17)      read: B1's reduction on xch     ev[7]    written: B1's accumulation      <- ev[13], as above
+  //   buf_a (k0), buf_l (xws[1])  read: A's, L's reductions (side) in order written: A's, L's accumulation  <- ev[13] (side is
+  //                                                                         in order: the sort follows the reductions)
+  //   h_dev (k0 slot 3)           read: sort of h on side         ev[15]   written: h-polynomial on main   (main waited ev[15])
+  //   st_h (k0 slots 4-6, 9, 25), buf_h (xws[0]), the record and the proof (k0 slot 16): read by H's reduction and the
+  //                               assembly on side2               ev[18]   the "tail fence" waits below, as before
+  //   w (the caller's)            read: w copy on side            ev[13]   the caller's next write, ordered on channel 0
+  //                                                                         behind this call, is behind main's wait for ev[13]
+  // ev[5] and ev[7] are waited for BEFORE this proof records them again, so the waits name the last proof's; a wait for an
+  // event that was never recorded, or whose work is done, costs nothing.  DG16_QUEUE_JOIN=1 restores the joins and the
+  // prologue on the main stream (the schedule every other form keeps).
+  static const bool queue_join = [] { const char* e = getenv("DG16_QUEUE_JOIN"); return e && atoi(e) != 0; }();
+  const bool queued = overlap_tail && !h_given && !dist && !queue_join;
+  Fr* h_dev = h_given ? nullptr : (Fr*)ws(k0.c, 3, rows * sizeof(Fr));
+  const Fr* h_scalars = h_in;
+  auto whole_h = [&] {
+    h_poly_launch(k0, CURVE, a_dev, b_dev, c_dev, log_m, h_dev);
+    h_scalars = h_dev + pk.h_lo;
+  };
+  const hipStream_t pro = queued ? side : main;      // the prologue's stream
+  if (queued) {
+    // ev[8] = entry: the caller's w is complete, the last proof's accumulations have read the sort this one rewrites.  The
+    // h-polynomial needs a, b, c only and is enqueued first: the main stream then has work while the host enqueues the rest.
+    DG_HIP(hipEventRecord(ev[8], main));
+    whole_h();
+    DG_HIP(hipStreamWaitEvent(side, ev[8], 0));
+    DG_HIP(hipStreamWaitEvent(side, ev[5], 0));      // the last proof's B reduction (st_ab, buf_b2)
+    DG_HIP(hipStreamWaitEvent(side, ev[7], 0));      // ... its B1 reduction and stage 1 (st_ab, buf_b1, r_s)
+  }
+  DG_HIP(hipMemcpyAsync(r_s, r_s_host, 2 * sizeof(Fr), hipMemcpyHostToDevice, pro));
+  DG_HIP(hipMemcpyAsync(sc_ab, w_dev + 1 + pk.ab_lo, n_ab * sizeof(Fr), hipMemcpyDeviceToDevice, pro));
+  hipLaunchKernelGGL(prover_scalar_prep_kernel<Fr>, dim3(1), dim3(1), 0, pro, r_s, sc_ab, n_ab, (int)mont,
+                     (int)(pk.shard + 1 == pk.nshards));
+  DG_HIP(hipGetLastError());
+  if (!queued) {
+    DG_HIP(hipEventRecord(ev[8], main));
+    DG_HIP(hipStreamWaitEvent(side, ev[8], 0));
+  }
+
   // side: the digit sort shared by A, B1, B and L; its buffers live in channel 1
-  DG_HIP(hipStreamWaitEvent(side, ev[8], 0));
   MsmSort st_ab = msm_sort_on<Fr, CT::SCALAR_BITS>(side, k1.c, sc_ab, n_ab + 3, mont, true, pk.c_ab, pk.stride);
   DG_HIP(hipEventRecord(ev[13], side));
   MsmBuffers<Fq2> buf_b2 = msm_buffers<Fq2>(k2.c, st_ab.g);
   buf_b2.busy_chip = true;
 
   // main: h (whole, or stage 0 of the sharded form)
-  Fr* h_dev = h_given ? nullptr : (Fr*)ws(k0.c, 3, rows * sizeof(Fr));
-  const Fr* h_scalars = h_in;
   if (dist) {
     const void* rows_in[3] = {a_dev, b_dev, c_dev};
     h_poly_dist_stage(k0, CURVE, log_m, rank, n_ranks, 0, rows_in, xbuf_a);
     exchange(3, 4);
-  } else if (!h_given) {
-    h_poly_launch(k0, CURVE, a_dev, b_dev, c_dev, log_m, h_dev);
-    h_scalars = h_dev + pk.h_lo;
+  } else if (!h_given && !queued) {
+    whole_h();
   }
   MsmSort st_h;
   const bool tail_fence = overlap_tail && ctx->tail_pending.load(std::memory_order_acquire);
@@ -508,8 +550,10 @@ static bool msms_typed(dg16_ctx* ctx, Call& k0, Call& k1, Call& k2, const PkDev&
   } else {
     msm_bucket_phase<Fq>(main, st_h, buf_h, false, res_h);
   }
-  DG_HIP(hipStreamWaitEvent(main, ev[10], 0));          // A, B1, L results, s*A, r*B1
-  DG_HIP(hipStreamWaitEvent(main, ev[5], 0));           // B result
+  if (!queued) {    // (a queue: channel 2's stream has waited for both, and the next proof fences what it reuses -- above)
+    DG_HIP(hipStreamWaitEvent(main, ev[10], 0));        // A, B1, L results, s*A, r*B1
+    DG_HIP(hipStreamWaitEvent(main, ev[5], 0));         // B result
+  }
   DG_HIP(hipGetLastError());
   return tail_on_side2;
 }

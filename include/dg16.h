@@ -79,7 +79,14 @@ enum dg16_flags {
                                stream instead of channel 0's, so the work enqueued next on channel 0 (the next proof's
                                dg16_qap and h-polynomial) starts under that latency-bound tail.  proof_out is complete
                                after dg16_sync(ctx, 2) (or stream-ordered work on channel 2); every other call on the
-                               context orders itself behind the tail.  Ignored with host pointers. */
+                               context orders itself behind the tail.  Ignored with host pointers.
+                               What is ordered where (dg16_groth16_prove, the whole h-polynomial): channel 0's stream carries
+                               the h-polynomial and the five accumulations and is NOT joined with the library's other streams
+                               when the call returns -- work enqueued on it afterwards is ordered behind this proof's last
+                               accumulation and behind its read of full_assignment, nothing else; channel 2's stream is
+                               ordered behind ALL of the proof (every reduction, the assembly, the copy to proof_out).  The
+                               next proof with this flag fences each workspace buffer at its first reuse.  DG16_QUEUE_JOIN=1 in the environment restores the join of
+                               channel 0 with the other streams at the end of the call (dg16_groth16_prove_dist keeps it). */
   DG16_F_BASES_IN_SUBGROUP = 64u /* dg16_msm, dg16_d_msm, dg16_prove_a / _b / _c: the caller guarantees that every base is
                                in the order-r subgroup (true of any arkworks G1Affine / G2Affine obtained through
                                Validate::Yes or from CRS generation).  The library may then split the scalars with the
