@@ -80,3 +80,47 @@ where
     })?;
     Ok(verdict.into_iter().map(|v| v == 1).collect())
 }
+
+/// One verdict for the whole batch (`dg16_groth16_verify_aggregate`): `Groth16::verify_proof` in a loop becomes one
+/// call.  `coeffs[i]` is proof i's 128-bit coefficient: the caller draws them independently and uniformly from
+/// [1, 2^128) AFTER the proofs are fixed (the library draws no randomness); a batch with an invalid proof is then
+/// accepted with probability about 2^-128, and equal or predictable coefficients void that.  A zero coefficient, a
+/// malformed proof or input is `false`, never an error of the call; on `false`, [`verify_batch`] says which proofs are bad.
+pub fn verify_aggregate<E, P1, P2>(pvk: &PreparedVk, inputs: &[Vec<E::ScalarField>], proofs: &[Proof<E>],
+                                   coeffs: &[u128]) -> Result<bool, Dg16Error>
+where
+    E: Pairing<G1Affine = Affine<P1>, G2Affine = Affine<P2>>,
+    P1: Dg16Config<ScalarField = E::ScalarField>,
+    P2: Dg16Config<ScalarField = E::ScalarField>,
+    P1::BaseField: FieldBytes,
+    P2::BaseField: FieldBytes,
+{
+    if inputs.len() != proofs.len() || coeffs.len() != proofs.len() {
+        return Err(Dg16Error::LengthMismatch(inputs.len().min(proofs.len()).min(coeffs.len())));
+    }
+    let mut x = Vec::with_capacity(proofs.len() * pvk.n_public * 32);
+    for row in inputs {
+        if row.len() != pvk.n_public {
+            return Err(Dg16Error::LengthMismatch(row.len().min(pvk.n_public)));
+        }
+        x.extend_from_slice(scalars_as_bytes(row));
+    }
+    let mut p = Vec::new();
+    for pr in proofs {
+        p.extend(pack_affine(&[pr.a]));
+        p.extend(pack_affine(&[pr.b]));
+        p.extend(pack_affine(&[pr.c]));
+    }
+    let mut rho = Vec::with_capacity(coeffs.len() * 16);
+    for c in coeffs {
+        rho.extend_from_slice(&c.to_le_bytes());
+    }
+    let mut accepted = 0u8;
+    check(unsafe {
+        sys::dg16_groth16_verify_aggregate(
+            CTX.0, pvk.h, x.as_ptr().cast(), pvk.n_public, p.as_ptr().cast(), proofs.len(), rho.as_ptr().cast(),
+            sys::DG16_F_SCALARS_MONT, &mut accepted, 0,
+        )
+    })?;
+    Ok(accepted == 1)
+}

@@ -297,6 +297,10 @@ extern "C" {
     pub fn dg16_groth16_verify_batch(ctx: *mut Dg16Ctx, vk: *const Dg16Vk, public_inputs: *const c_void,
                                      n_public: usize, proofs_affine: *const c_void, n_proofs: usize, flags: c_uint,
                                      verdict: *mut u8, channel: c_int) -> c_int;
+    pub fn dg16_groth16_verify_aggregate(ctx: *mut Dg16Ctx, vk: *const Dg16Vk, public_inputs: *const c_void,
+                                         n_public: usize, proofs_affine: *const c_void, n_proofs: usize,
+                                         coeffs: *const c_void, flags: c_uint, accepted: *mut u8, channel: c_int)
+                                         -> c_int;
     // ---- dist-primitives over an MpcNet (packed secret sharing): d_fft, d_msm, d_pp, deg_red, ext_wit::h, prove::A/B/C ----
     pub fn dg16_pss_create(ctx: *mut Dg16Ctx, curve: c_int, l: c_uint, out: *mut *mut Dg16Pss) -> c_int;
     pub fn dg16_d_fft(ctx: *mut Dg16Ctx, pp: *const Dg16Pss, net: *const Dg16Net, share: *const c_void,

@@ -80,6 +80,10 @@ bool vk_prepare<DG_CURVE>(const void* alpha_g1, const void* beta_g2, const void*
   std::vector<P::Line> tg(P::N_LINES), td(P::N_LINES);
   P::Fq12 ab;
   if (!P::prepare_key(alpha, beta, gamma, delta, icv.data(), n_ic, tg.data(), td.data(), &ab)) return false;
+  // the aggregate verifier's third pair (aggregate_curve.hip): beta's lines and -alpha
+  std::vector<P::Line> tb(P::N_LINES);
+  if (!beta.is_inf()) P::prepare_g2(beta, tb.data());
+  Affine<Fq> nalpha = alpha.is_inf() ? alpha : Affine<Fq>{alpha.x, alpha.y.neg()};
   VkData d;
   try {
     d.n_ic = n_ic;
@@ -87,6 +91,8 @@ bool vk_prepare<DG_CURVE>(const void* alpha_g1, const void* beta_g2, const void*
     if (!gamma.is_inf()) d.gamma = upload(tg.data(), tg.size() * sizeof(P::Line));
     if (!delta.is_inf()) d.delta = upload(td.data(), td.size() * sizeof(P::Line));
     d.alpha_beta = upload(&ab, sizeof ab);
+    if (!beta.is_inf()) d.beta = upload(tb.data(), tb.size() * sizeof(P::Line));
+    d.neg_alpha = upload(&nalpha, sizeof nalpha);
   } catch (...) {
     vk_release(d);
     throw;

@@ -6,12 +6,6 @@
 
 #include "verify_batch.h"
 
-struct dg16_vk {
-  dg16_ctx* ctx = nullptr;
-  int curve = 0;
-  dg16::VkData d;
-};
-
 using namespace dg16;
 
 extern "C" {

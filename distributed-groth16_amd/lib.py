@@ -238,6 +238,7 @@ def load():
     L.dg16_vk_destroy.argtypes = [vp]
     L.dg16_vk_destroy.restype = None
     L.dg16_groth16_verify_batch.argtypes = [vp, vp, vp, sz, vp, sz, u, vp, i]
+    L.dg16_groth16_verify_aggregate.argtypes = [vp, vp, vp, sz, vp, sz, vp, u, vp, i]
     _lib = L
     return L
 
@@ -261,7 +262,7 @@ EXPORTED = ["dg16_ctx_create", "dg16_ctx_destroy", "dg16_last_error", "dg16_set_
             "dg16_zkey_free", "dg16_serialize_error", "dg16_proof_compress", "dg16_proof_decompress",
             "dg16_verify_error", "dg16_groth16_verify", "dg16_prove_a", "dg16_prove_b", "dg16_prove_c",
             "dg16_ctx_set_table_budget", "dg16_fixed_base_mul", "dg16_fixed_base_window_bits", "dg16_groth16_setup",
-            "dg16_vk_create", "dg16_vk_destroy", "dg16_groth16_verify_batch"]
+            "dg16_vk_create", "dg16_vk_destroy", "dg16_groth16_verify_batch", "dg16_groth16_verify_aggregate"]
 
 
 def _ptr(x):

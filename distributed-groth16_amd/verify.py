@@ -1,11 +1,12 @@
 """Groth16 verification through libdg16 -- the counterpart of `Groth16::<E>::verify_proof` as the reference calls it
 (groth16/examples/sha256.rs:228-254, the verify endpoint of mpc-api/src/main.rs, zk-cli verify).  Two paths:
 `verify_proof` / `verify_with_zkey`: the host verifier (`dg16_groth16_verify`, csrc/verify.hip; BN254, one proof per
-call); `PreparedVerifyingKey`: batches on the GPU (`dg16_vk_create` + `dg16_groth16_verify_batch`; BN254 and
-BLS12-381).  Points are affine x || y Montgomery limbs (uint64), the layout of a zkey's header / IC section and of
+call); `PreparedVerifyingKey`: batches on the GPU (`dg16_vk_create` + `dg16_groth16_verify_batch` for one verdict
+per proof, `dg16_groth16_verify_aggregate` for one verdict per batch; BN254 and BLS12-381).  Points are affine x || y Montgomery limbs (uint64), the layout of a zkey's header / IC section and of
 `serialize.decompress_to_limbs`."""
 
 import ctypes
+import secrets
 
 import numpy as np
 
@@ -36,6 +37,15 @@ def verify_with_zkey(zkey, public_inputs, proof_affine, scalars_mont=False):
     """Verification key taken from a parsed `.zkey` (zkey.ZKey): alpha, beta, gamma, delta and IC as they lie in it."""
     return verify_proof(zkey.alpha_g1, zkey.beta_g2, zkey.gamma_g2, zkey.delta_g2, zkey.ic, public_inputs,
                         proof_affine, scalars_mont=scalars_mont)
+
+
+def random_coefficients(n):
+    """n nonzero 128-bit coefficients for `verify_aggregate` from the operating system's generator: n x 2 uint64."""
+    buf = bytearray(secrets.token_bytes(16 * n))
+    for i in range(n):
+        while not any(buf[16 * i:16 * i + 16]):
+            buf[16 * i:16 * i + 16] = secrets.token_bytes(16)
+    return np.frombuffer(bytes(buf), dtype=np.uint64).reshape(n, 2)
 
 
 class PreparedVerifyingKey:
@@ -98,6 +108,49 @@ class PreparedVerifyingKey:
         p = lambda x: x.ctypes.data_as(ctypes.c_void_p)
         ctx._chk(L.dg16_groth16_verify_batch(ctx.h, self.h, p(pub), n_public, p(proofs), n, flags, p(out), channel))
         return out[:n].astype(bool)
+
+    def verify_aggregate(self, public_inputs, proofs, coeffs=None, scalars_mont=False, device=False, channel=0,
+                         n_proofs=None):
+        """One verdict for the whole batch (`dg16_groth16_verify_aggregate`): True iff every proof passes the input
+        checks and the random linear combination of the verification equations holds.  Layouts as `verify_batch`.
+        coeffs: n_proofs x 2 uint64 (128-bit little-endian coefficients); None draws nonzero ones from `secrets` --
+        coefficients must be unpredictable and chosen after the proofs are fixed, or the verdict guarantees nothing
+        (include/dg16.h).  device=True: public_inputs, proofs and coeffs are device pointers, coeffs and n_proofs are
+        required, and the verdict is read back after the channel has drained.  On False, `verify_batch` says which
+        proofs are bad."""
+        flags = _lib.F_SCALARS_MONT if scalars_mont else 0
+        L, ctx = self.ctx.L, self.ctx
+        if device:
+            import torch
+            ptr = lambda x: x.data_ptr() if hasattr(x, "data_ptr") else int(x or 0)
+            if n_proofs is None or coeffs is None:
+                raise ValueError("n_proofs and coeffs are required with device pointers")
+            out = torch.zeros(1, dtype=torch.uint8, device="cuda:%d" % self.ctx.device)
+            ctx._chk(L.dg16_groth16_verify_aggregate(ctx.h, self.h, ctypes.c_void_p(ptr(public_inputs)), self.n_public,
+                                                     ctypes.c_void_p(ptr(proofs)), n_proofs,
+                                                     ctypes.c_void_p(ptr(coeffs)), flags | _lib.F_DEVICE_PTRS,
+                                                     ctypes.c_void_p(out.data_ptr()), channel))
+            ctx.sync(channel)
+            return bool(out.cpu()[0])
+        proofs = np.ascontiguousarray(proofs, dtype=np.uint64).reshape(-1, 8 * self.fq)
+        n = proofs.shape[0]
+        pub = np.ascontiguousarray(public_inputs, dtype=np.uint64)
+        if n == 0:
+            n_public = self.n_public
+        elif pub.size % (4 * n):
+            raise ValueError("public_inputs is not n_proofs x n_public scalars")
+        else:
+            n_public = pub.size // (4 * n)      # the library compares it with the key (LENGTH_MISMATCH)
+        if coeffs is None:
+            coeffs = random_coefficients(n)
+        coeffs = np.ascontiguousarray(coeffs, dtype=np.uint64).reshape(-1, 2)
+        if coeffs.shape[0] != n:
+            raise ValueError("coeffs is not n_proofs x 2 uint64")
+        out = np.zeros(1, dtype=np.uint8)
+        p = lambda x: x.ctypes.data_as(ctypes.c_void_p)
+        ctx._chk(L.dg16_groth16_verify_aggregate(ctx.h, self.h, p(pub), n_public, p(proofs), n, p(coeffs), flags,
+                                                 p(out), channel))
+        return bool(out[0])
 
     def close(self):
         if self.h:

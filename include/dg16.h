@@ -602,7 +602,8 @@ int dg16_groth16_verify(int curve, const void *alpha_g1, const void *beta_g2, co
  * not fail the batch).  Identity points in a proof are legal: the verdict is what the equation gives.
  * DG16_F_SCALARS_MONT as everywhere; host pointers: synchronous; DG16_F_DEVICE_PTRS: stream-ordered on `channel`,
  * verdict a device pointer (16-byte aligned inputs and proofs).  Temporaries come from the channel's workspace
- * (DG16_ERR_OOM leaves the context usable).  Per-proof verdicts only: no random-linear-combination batching. */
+ * (DG16_ERR_OOM leaves the context usable).  Per-proof verdicts only; dg16_groth16_verify_aggregate below gives ONE
+ * verdict for the whole batch by random-linear-combination batching. */
 typedef struct dg16_vk dg16_vk;
 int dg16_vk_create(dg16_ctx *ctx, int curve, const void *alpha_g1, const void *beta_g2, const void *gamma_g2,
                    const void *delta_g2, const void *ic, size_t n_ic, unsigned flags, dg16_vk **out);
@@ -610,6 +611,32 @@ void dg16_vk_destroy(dg16_vk *vk);
 int dg16_groth16_verify_batch(dg16_ctx *ctx, const dg16_vk *vk, const void *public_inputs, size_t n_public,
                               const void *proofs_affine, size_t n_proofs, unsigned flags, uint8_t *verdict,
                               int channel);
+
+/* ---- Aggregate Groth16 verification: one verdict for a batch (BN254 and BLS12-381) ---------------------------------
+ *   dg16_groth16_verify_aggregate  <- Groth16::verify_proof in a loop whose caller only asks "is the whole batch valid?"
+ * The small-exponent test (what bellman's verify_proofs_batch does on the CPU): with coefficients rho_i,
+ *   prod_i e(rho_i A_i, B_i) * e(-sum_j s_j IC_j, gamma) * e(-sum_i rho_i C_i, delta) * e(-s_0 alpha, beta) == 1,
+ *   s_j = sum_i rho_i x_ij mod r, x_i0 = 1 (so s_0 = sum_i rho_i)
+ * -- per proof one Miller loop, per batch two MSMs, three Miller loops from the key's line tables and ONE final
+ * exponentiation.  Key handle, point layout, input layout, curves and DG16_F_SCALARS_MONT / DG16_F_DEVICE_PTRS (the only
+ * flags accepted) are those of dg16_groth16_verify_batch; coeffs = n_proofs x 16 bytes, each a little-endian unsigned
+ * 128-bit integer; accepted = ONE byte.  With DG16_F_DEVICE_PTRS the call is stream-ordered on `channel` and coeffs and
+ * accepted are device pointers too (16-byte aligned coeffs).  Temporaries come from the channel's workspace
+ * (DG16_ERR_OOM leaves the context usable).
+ * *accepted = 1 iff (a) EVERY proof passes the per-proof input checks of dg16_groth16_verify_batch (reduced coordinates,
+ * points on their curves, B in G2, on BLS12-381 A and C in G1, every public input < r) and (b) the combined equation
+ * holds.  Anything wrong with any proof is *accepted = 0 and DG16_OK, not an error.  A zero coefficient is
+ * *accepted = 0 (a proof is never silently skipped); n_proofs = 0 is *accepted = 1; n_public + 1 != n_ic returns
+ * DG16_ERR_LENGTH_MISMATCH.  Identity points in a proof are legal: the equation decides.
+ * THE COEFFICIENTS ARE THE CALLER'S: the library draws no randomness (as dg16_groth16_prove takes r and s).  The
+ * contract: the rho_i are independent and uniform in [1, 2^128), and they are chosen AFTER the proofs are fixed.  A batch
+ * that holds an invalid proof is then accepted with probability about 2^-128.  Equal or predictable coefficients void
+ * the guarantee (two tampered proofs whose errors cancel under equal coefficients pass).  On *accepted = 0,
+ * dg16_groth16_verify_batch says which proofs are bad. */
+int dg16_groth16_verify_aggregate(dg16_ctx *ctx, const dg16_vk *vk, const void *public_inputs, size_t n_public,
+                                  const void *proofs_affine, size_t n_proofs,
+                                  const void *coeffs /* n_proofs x 16 bytes, little-endian unsigned */, unsigned flags,
+                                  uint8_t *accepted /* ONE byte */, int channel);
 
 /* Duration in milliseconds of the dominant kernel(s) of the most recent call on `channel`
  * (HIP events recorded on the channel's stream); 0 if none.  which: 0 = whole call,
