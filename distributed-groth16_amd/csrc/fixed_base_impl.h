@@ -4,7 +4,7 @@
 //   table    T[w][d - 1] = d * 2^(c w) * B, d = 1 .. 2^(c-1), w < nwin = ceil((bits + 1) / c), affine, built per call:
 //            one lane per window doubles B up to 2^(c w) B (fb_window_bases_kernel), then one lane per run of
 //            kFbChunk consecutive multiples walks them by mixed additions and converts the run to affine with ONE
-//            inversion (fb_table_kernel; the walk and Montgomery's trick of gen_bases_kernel, msm_impl.h).
+//            inversion (fb_table_kernel; the walk and Montgomery's trick of gen_bases_kernel, msm_table.h).
 //   multiply one lane per output point: the scalar is recoded into signed c-bit digits d_w in [-2^(c-1), 2^(c-1)]
 //            (k = sum d_w 2^(c w); nwin c >= bits + 1 leaves room for the last carry), and the lane adds
 //            T[w][|d_w| - 1] (negated for d_w < 0) into an XYZZ accumulator: nwin mixed additions, NO doublings.

@@ -64,7 +64,7 @@ DG_HD bool magnitude(const uint32_t* acc, uint32_t* out) {
 }
 
 // k (8 words, < 2^256) -> |k1|, |k2| as 8-word integers with the sign in bit 255 of each: the form the digit kernels of
-// msm_impl.h take (a set bit 255 negates every digit of the scalar; a canonical field element never has it set)
+// msm_sort.h take (a set bit 255 negates every digit of the scalar; a canonical field element never has it set)
 template <class GC>
 DG_HD void split(const uint32_t* k, uint32_t* h1, uint32_t* h2) {
   uint32_t t[13], c1[5], c2[5];

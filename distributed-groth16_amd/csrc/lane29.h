@@ -4,7 +4,7 @@
 // EVERY function below assumes all 64 lanes of the wave active and its operands uniform across the four rows (unless a
 // product has just put four different results on them): the row primitives are opaque asm that reads other lanes.
 //
-// The wave-cooperative chains of msm_impl.h (dbl_wave29 / add_wave29) run one base-field product per LANE: a level of
+// The wave-cooperative chains of msm_chains.h (dbl_wave29 / add_wave29) run one base-field product per LANE: a level of
 // a group operation is then never shorter than one 162-mad product on one lane (227 dependent VALU issues, 0.45 us) plus
 // ~36 DPP moves and the selects that route nine-register values between slots (0.79 us as built).  Here a field element
 // is ONE register: lane i of a row of 16 lanes holds limb i (W = 29, nine limbs; lanes 9..15 hold zero), and a
@@ -970,7 +970,7 @@ template <class F> using Ops = typename PolicyOf<F>::type;
 // which coordinate fields run their chains in this form: nine-limb fields (BN254: Fq, and Fq2 with u^2 = -1)
 template <class F>
 constexpr bool enabled() {
-#ifdef DG16_NO_LANE_CHAINS        // (A/B switch: the one-product-per-lane chains of msm_impl.h everywhere)
+#ifdef DG16_NO_LANE_CHAINS        // (A/B switch: the one-product-per-lane chains of msm_chains.h everywhere)
   return false;
 #else
   using P = typename FieldOf<F>::Params;

@@ -55,7 +55,7 @@ void DG_FN(msm_resident_)(Call& k, const void* table, size_t n, unsigned c, unsi
 
 // The king's combination "in the exponent" when there are FEW outputs (d_msm: one; unpackexp of a handful of elements):
 // out[e][r] = sum_c M[r][c] P[e][c] with one WORKGROUP per output and one WAVE per term -- the scalar multiples run side
-// by side as wave-cooperative width-4 NAF chains on the reduced-radix types (msm_impl.h: scalar_mul_wave29), then wave 0
+// by side as wave-cooperative width-4 NAF chains on the reduced-radix types (msm_chains.h: scalar_mul_wave29), then wave 0
 // adds the terms.  Round 6: the lane-per-output kernel of dist_impl.h (matvec_points_kernel: right for thousands of
 // outputs) ran d_msm's single output as EIGHT full scalar multiplications one after another on ONE lane on 32-bit limbs --
 // ~80 ms for BLS12-377 G1 whatever the size of the MSM in front of it (bench.py's dmsm_sweep: 81-99 ms per round at

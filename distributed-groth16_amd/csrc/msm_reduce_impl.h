@@ -20,13 +20,13 @@ namespace dg16 {
 // <= kGiantSlices slices, one workgroup each, and leaves every slice's sum IN PLACE in the slice's first
 // segment slot; stage 2 adds the slice sums.  (One workgroup per bucket chained 128 dependent additions per
 // lane for a 2^20-bit witness: 2.5 ms for G1, far more for G2.)
-// (kGiantSlices, kGiantSliceSegs, giant_geometry: msm_impl.h -- the throughput finalize there registers giants too)
+// (kGiantSlices, kGiantSliceSegs, giant_geometry: msm_geom.h -- the throughput finalize of msm_finalize.h registers giants too)
 
 // ---- 4b / 5: bucket reduction --------------------------------------------------------------------------------
 // sum_b (b + 1) B_b over the 2^(c-1) buckets of a bucket-window, B_b = sum of the bucket's segment partials.
 // Every phase is a short chain of dependent group operations (a lone lane needs ~5 us per G1 addition, ~15 us per
 // G2 addition), so the work is arranged for the shortest chains, not the fewest additions:
-//   finalize    one lane per bucket (msm_impl.h: msm_finalize_thr_kernel)
+//   finalize    one lane per bucket (msm_finalize.h: msm_finalize_thr_kernel)
 //   giants      buckets with > kGiantSegs partials (boolean witnesses, short top windows): device-side work list,
 //               one workgroup per slice, then one fold per giant (unchanged idea, see giant_geometry)
 //   row         one workgroup per ROW of 256 buckets: suffix scan S_c = sum_{c' >= c} B_c' (8 steps) gives the row
@@ -135,7 +135,7 @@ __global__ void __launch_bounds__(64) msm_giant_fold_kernel(MsmGeom g, unsigned 
 
 
 // A narrow tree step, sh[base + i] += sh[base + i + d] for i < d <= 64, on ROWS OF 16 LANES: a lone lane takes ~10 us (G1) /
-// ~35 us (G2) per dependent addition whatever the number of idle lanes around it; add_wave29 (msm_impl.h) spreads the four
+// ~35 us (G2) per dependent addition whatever the number of idle lanes around it; add_wave29 (msm_chains.h) spreads the four
 // product levels of ONE addition over the 16 lanes of a row -- its operands only have to be uniform within the row: the
 // broadcasts are row_newbcast, the Fq2 product's shuffles stay inside a quad -- ~3 us (G1) / ~8 us (G2, products behind
 // calls in this unit).  Sixteen rows of a 256-lane half take additions i = row, row + 16, ..: steps of <= 16 additions
@@ -361,7 +361,7 @@ __global__ void __launch_bounds__(256 * HALVES) msm_top_kernel(TopGeom tg, const
     }
   }
   // The last final_log + 1 operations are a chain on ONE value: the wave that holds it runs them wave-cooperatively
-  // (msm_impl.h: dbl_wave29 / add_wave29 -- ~1.5 us per G1 operation against ~11 us for a lone lane's, G2 3 against 25)
+  // (msm_chains.h: dbl_wave29 / add_wave29 -- ~1.5 us per G1 operation against ~11 us for a lone lane's, G2 3 against 25)
   constexpr unsigned RES = HALVES == 2 ? 256u : 0u;
   if ((threadIdx.x >> 6) == (RES >> 6)) {
     if constexpr (lane29::enabled<F>()) {        // limb-per-lane chain (lane29.h)
@@ -503,9 +503,6 @@ __global__ void __launch_bounds__(64) msm_lane_reduce_serial_kernel(const XYZZ29
     // (default priority ON PURPOSE: inside a queue of proofs these reductions have slack and the accumulations they run
     // beside do not -- at s_setprio 3 an 8-shard rank took 2.56-2.59 ms per proof, at 0 2.50-2.51, a 4-shard rank 3.78 against
     // 3.63, config 4 in a queue 1.65 against 1.61: profiles/r6hh_serial_reduce_prio_ab.txt)
-#ifdef DG16_SERIAL_REDUCE_PRIO
-    __builtin_amdgcn_s_setprio(DG16_SERIAL_REDUCE_PRIO);
-#endif
     const unsigned G = 1u << g_log;
     typename FO::KT kc;
     kc.init();
@@ -641,7 +638,7 @@ void msm_bucket_phase(hipStream_t s, const MsmSort& st, const MsmBuffers<F>& b, 
   DG_BOUNDS_BIND();
   trace_point(s, "(before bucket phase)");
   if constexpr (FieldOf<F>::EXT) {
-    // G2: the throughput finalize ran behind the accumulation, on its stream (msm_impl.h: msm_finalize_lds_phase)
+    // G2: the throughput finalize ran behind the accumulation, on its stream (msm_finalize.h: msm_finalize_lds_phase)
   } else {
     DG_HIP(hipMemsetAsync(b.giant, 0, 8, s));
     msm_finalize_phase<F>(s, st, b);        // inline products (msm_group.hip)

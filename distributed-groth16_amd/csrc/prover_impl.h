@@ -56,7 +56,7 @@ __device__ XYZZ<F> mul_by_fr(const XYZZ<F>& p, const Fr& k_canon) {
 constexpr int kRecA = 0, kRecB1 = 1, kRecL = 2, kRecH = 3, kRecSA = 4, kRecRB1 = 5, kRecG1 = 6;
 
 // which = 0: A' = msm (+ alpha_g1 + a_query[0] on shard 0), s*A';  which = 1: B1' (+ beta_g1 + b_g1_query[0]),
-// r*B1'.  One wave each: the doublings and additions of the scalar multiple run wave-cooperatively (msm_impl.h:
+// r*B1'.  One wave each: the doublings and additions of the scalar multiple run wave-cooperatively (msm_chains.h:
 // scalar_mul_wave29 -- round 6: 127 doublings + ~51 additions for BN254 instead of 254 + ~127).
 template <class Fq, class Fr>
 __global__ void __launch_bounds__(128) prover_stage1_g1_kernel(Jacobian<Fq>* rec, const Affine<Fq>* fixed_g1,
@@ -72,10 +72,10 @@ __global__ void __launch_bounds__(128) prover_stage1_g1_kernel(Jacobian<Fq>* rec
   }
   const Fr k = which == 0 ? s : r;
   // (the chain runs on the reduced-radix types, over width-4 NAF digits and -- BN254 -- the two halves of the endomorphism
-  // split: msm_impl.h: scalar_mul_wave29)
+  // split: msm_chains.h: scalar_mul_wave29)
   __shared__ ScalarMulLds<Fq> lds;
   XYZZ<Fq> kv;
-  if constexpr (scalar_mul_splits<Fq>()) {       // two waves per chain: one half of the split scalar each (msm_impl.h)
+  if constexpr (scalar_mul_splits<Fq>()) {       // two waves per chain: one half of the split scalar each (msm_chains.h)
     __shared__ XYZZ29<Fq> xchg;
     kv = scalar_mul_two_waves29<Fq, Fr::NL>(XYZZ29<Fq>::from_xyzz32(v), k.l, &lds, &xchg).to_xyzz32();
   } else {
@@ -100,7 +100,7 @@ __global__ void __launch_bounds__(64) prover_stage1_g2_kernel(Jacobian<Fq2>* msm
 
 // ---- the assembly's chains: wave-cooperative operations on the reduced-radix types, products behind a call ----------
 // The assembly runs ONCE per proof on a few waves: what it costs is dependent issue plus the fetch of cold code, so every
-// level's product goes through one out-of-line copy per field (msm_impl.h: add_wave29<F, SlotMulCall>) and the kernel
+// level's product goes through one out-of-line copy per field (msm_chains.h: add_wave29<F, SlotMulCall>) and the kernel
 // stays a few KB.
 // (operands as 16-lane vectors: hipcc passes aggregates beyond 16 dwords per call through scratch, vectors in VGPRs)
 typedef uint32_t limbs16_t __attribute__((ext_vector_type(16)));

@@ -1,5 +1,5 @@
 """The limb-per-lane chains of csrc/lane29.h on the GPU, against the one-product-per-lane chains they replace
-(msm_impl.h: dbl_wave29 / add_wave29, themselves pinned to the oracle by the MSM and prover suites): the row primitives
+(msm_chains.h: dbl_wave29 / add_wave29, themselves pinned to the oracle by the MSM and prover suites): the row primitives
 (DPP row shifts / rotations, v_permlane16/32_swap) lane by lane, 4096 products, and for every group the chains cover
 (G1 and G2 of BN254, BLS12-381, BLS12-377) 1024 doublings, additions, p + p, p - p, identity operands and a chain of
 48 doublings + 3 additions and the affine form (an inversion in lane form).  The program is tools/ubench/lane29_probe (built by csrc/Makefile).  End-to-end parity of the

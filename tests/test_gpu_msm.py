@@ -415,7 +415,7 @@ def test_resident_msm_2e20_equals_plain_msm():
 @pytest.mark.parametrize("curve,n", [("bn254", 1 << 13), ("bn254", (1 << 15) + 7), ("bn254", 1 << 16), ("bn254", 1 << 17),
                                       ("bls12_377", 1 << 14), ("bls12_381", 1 << 13), ("bls12_381", 1 << 15)])
 def test_short_table_window_rule_and_its_plan_mirror(curve, n):
-    """The window width of SHORT resident tables (csrc/msm_impl.h: msm_window_bits with the scalar width -- the width whose top
+    """The window width of SHORT resident tables (csrc/msm_geom.h: msm_window_bits with the scalar width -- the width whose top
     window is not a handful of giant buckets: 15 for BN254 / BLS12-377 keys of 2^13 .. 2^16 points, lg + 1 for BLS12-381):
     the library's own report == the mirror `bench.py --dry-run` plans with, and the resident MSM at that width == dg16_msm
     (oracle-checked above) for G1."""
@@ -450,7 +450,7 @@ def test_short_table_window_rule_and_its_plan_mirror(curve, n):
                                       ("bls12_381", (1 << 18) - 5)])
 def test_plain_g1_msm_at_the_sixteen_bit_window_sizes(curve, n):
     """Plain G1 MSMs of 2^17 .. 2^18 points run the split halves with c = 16 (eight windows of the 128-bit halves instead of
-    log2(2 n) - 4 = 14 / 15: csrc/msm_impl.h, msm_run): against the oracle's MSM, through the host-pointer entry."""
+    log2(2 n) - 4 = 14 / 15: csrc/msm_geom.h, msm_plain_plan): against the oracle's MSM, through the host-pointer entry."""
     bases = ctx().gen_bases(curve, 1, 2 + n, n)
     scalars = corc.rand_field(curve, "fr", 9 + n, n, mont=False)
     jac = gmsm(ctx(), curve, 1, bases, scalars)

@@ -260,7 +260,7 @@ def test_point_codec_host_bls12_381_zcash_form(ha, group):
 def test_glv_split_is_exact_and_short(ha, curve):
     """csrc/glv.h: k = k1 + k2 LAMBDA (mod r) for every scalar, the halves equal the same integer arithmetic done with
     Python integers on the constants of the header (division-free rounding included), and |k1|, |k2| < 2^127 -- the
-    bound kGlvBits of msm_impl.h rests on -- over edge values, every 255-bit corner and 200 000 random scalars."""
+    bound kGlvBits of msm_geom.h rests on -- over edge values, every 255-bit corner and 200 000 random scalars."""
     import re
     hdr = os.path.join(HERE, "..", "distributed-groth16_amd", "csrc", "consts_gen.h")
     text = open(hdr).read()
@@ -295,7 +295,7 @@ def test_glv_split_is_exact_and_short(ha, curve):
 def test_glv_split4_is_exact_and_short(ha, curve):
     """csrc/glv.h: the four-dimensional split of G2 scalars -- k = sum_j k_j LAMBDA^j (mod r) for every scalar, the quarters
     equal the same integer arithmetic done with Python integers on the constants of the header, and |k_j| < 2^65 (the
-    bound kGlv4Bits of msm_impl.h rests on)."""
+    bound kGlv4Bits of msm_geom.h rests on)."""
     import re
     hdr = os.path.join(HERE, "..", "distributed-groth16_amd", "csrc", "consts_gen.h")
     text = open(hdr).read()

@@ -469,7 +469,7 @@ def test_bucket_reduction_workgroups(group, chunked):
 
 def test_horner_tail_on_one_wave():
     """msm_tail_kernel (G1 of BN254) on the Workgroup emulator: one wave runs the Horner chain over the window sums with
-    the wave-cooperative operations on the reduced-radix types (msm_impl.h: dbl_wave29 / add_wave29 -- a dependency level
+    the wave-cooperative operations on the reduced-radix types (msm_chains.h: dbl_wave29 / add_wave29 -- a dependency level
     is one product per lane, the slots are joined with v_mov_b32_dpp row_newbcast): 2^c (2^c S_2 + S_1) + S_0 == the oracle's, for window
     sums in XYZZ form with Z != 1, one of them the identity's neighbour case S_1 = S_2 (the addition's doubling branch)."""
     import random

@@ -440,7 +440,7 @@ def test_channel_watchdog_lands_every_party_on_the_serial_form(stall):
 
 def test_bench_dry_run_plan_matches_the_keys_the_gpu_built():
     """`bench.py --gpus N --dry-run` touches no GPU and prints the plan of the run: per-rank shard sizes, window bits and
-    table bytes by the formulas of csrc/prover_impl.h / msm_impl.h.  Pinned against what the library itself reported for
+    table bytes by the formulas of csrc/prover_impl.h / msm_geom.h.  Pinned against what the library itself reported for
     keys it built on the GPU (profiles/): BN254 2^20 one key 6 039 807 360 B (r5z_bench_line.json), BLS12-381 2^20 over 8
     shards 9 663 853 056 B, 2^24 over 8 shards 144 955 311 840 B (r5g_*_full_parity.json)."""
     import json

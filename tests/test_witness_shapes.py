@@ -1,6 +1,6 @@
 """The helpers of test_gpu_witness_shapes.py, on the host: the witness-shaped scalars are canonical, the digit mirror is
 msm_digit's recoding, the boundary scalars carry the digits they are built for, and the geometry mirror puts each GPU
-case on the reduction path that file claims for it -- so a later change of csrc/msm_impl.h's geometry fails here
+case on the reduction path that file claims for it -- so a later change of csrc/msm_geom.h's geometry fails here
 instead of leaving a GPU test that silently stopped reaching its path."""
 
 import numpy as np

@@ -3,9 +3,9 @@
 A circom witness is mostly bits, some small integers and some field negatives r - k: the scalars of four of the
 prover's five MSMs (A, B1, B2, L).  Such scalars put almost every bucket entry into one bucket and leave the others
 empty -- paths that uniform random scalars reach only by chance.  This module makes those scalars (`shape`), mirrors
-the signed-digit recoding of csrc/msm_impl.h (`digits`, `msm_digit`), builds scalars whose digits sit on the recoding's
-edges (`boundary_scalars`), and mirrors the segment / partial arithmetic of `msm_geometry` (`geometry`, `plain_geometry`,
-`bucket_regime`) so that a test can assert which reduction path a GPU case reaches.
+the signed-digit recoding of csrc/msm_sort.h (`digits`, `msm_digit`), builds scalars whose digits sit on the recoding's
+edges (`boundary_scalars`), and mirrors the planning arithmetic of csrc/msm_geom.h (`window_bits`, `geometry`,
+`plain_geometry`, `giant_slices`; tests/test_msm_geom_host.py holds the two equal) and the partial counts (`bucket_regime`) so that a test can assert which reduction path a GPU case reaches.
 """
 
 import numpy as np
@@ -18,7 +18,7 @@ KINDS = ("bits", "ones", "sparse", "u32", "u64", "neg_small", "const", "sha256_m
 # the shape seeds of test_gpu_witness_shapes.py's cases: test_witness_shapes.py mirrors exactly those scalars
 SEEDS = {"plain": 1, "giant": 2, "subgroup": 3, "resident": 4, "budget": 5, "proof": 10}
 
-# csrc/msm_impl.h
+# csrc/msm_geom.h
 K_MIN_SEG_LOG, K_MAX_SEG_LOG = 3, 9
 K_MIN_LANES_LOG = 18
 K_GIANT_SEGS = 64
@@ -98,7 +98,7 @@ def shape(curve, n, kind, seed=0):
     return out
 
 
-# ---- the signed-digit recoding (csrc/msm_impl.h: msm_digit, msm_digits_kernel) -----------------------------------
+# ---- the signed-digit recoding (csrc/msm_sort.h: msm_digit, msm_digits_kernel) -----------------------------------
 def nwin_of(c, bits):
     return (bits + 1 + c - 1) // c          # one spare bit absorbs the last carry
 
@@ -192,7 +192,7 @@ def boundary_scalars(c, bits, n, curve, seed=0):
     return _to_limbs(vals)
 
 
-# ---- geometry (csrc/msm_impl.h: msm_window_bits, msm_geometry; msm_run's choice of width and GLV split) ----------------
+# ---- geometry (csrc/msm_geom.h: msm_window_bits, msm_geometry; msm_plain_plan: msm_run's choice of width and GLV split) --
 def window_bits(n, table, scalar_bits=0):
     lg = max(n, 1).bit_length() - 1
     if n > (3 << lg) // 2:
@@ -275,6 +275,13 @@ def _glv_trivial(scalars, dim):
     return np.concatenate([s] + [np.zeros_like(s)] * (dim - 1))
 
 
+def giant_slices(nseg):
+    """giant_geometry: a giant bucket's nseg partials in at most K_GIANT_SLICES slices of `per` partials."""
+    slices = min((nseg + K_GIANT_SLICE_SEGS - 1) // K_GIANT_SLICE_SEGS, K_GIANT_SLICES)
+    per = (nseg + slices - 1) // slices
+    return (nseg + per - 1) // per, per
+
+
 def bucket_regime(g, scalars, wg_log, ninst=1):
     """Which finalize / giant paths the sort of `scalars` (the sort's own input: halves for GLV) reaches in geometry g.
     Mirrors the histogram, the segment-count scan (seg_off) and msm_nparts / giant_geometry."""
@@ -290,10 +297,7 @@ def bucket_regime(g, scalars, wg_log, ninst=1):
     first = np.cumsum(k, axis=1) - k                          # exclusive scan per bucket-window
     np_ = np.where(k > 0, ((first + k - 1) >> wg_log) - (first >> wg_log) + 1, 0)
     giants = np_ > K_GIANT_SEGS
-    pers = []
-    for v in np_[giants]:
-        slices = min((int(v) + K_GIANT_SLICE_SEGS - 1) // K_GIANT_SLICE_SEGS, K_GIANT_SLICES)
-        pers.append((int(v) + slices - 1) // slices)
+    pers = [giant_slices(int(v))[1] for v in np_[giants]]
     return {"c": c, "seg_log": seg_log, "buckets": bw * nb, "nonempty": int((counts > 0).sum()),
             "max_count": int(counts.max()), "max_np": int(np_.max()), "giants": int(giants.sum()) * ninst,
             "max_per": max(pers) if pers else 0, "stitched": int(((np_ >= 2) & ~giants).sum()),

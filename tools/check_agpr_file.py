@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Build-time check of the accumulation-register file of msm_impl.h (acc_set / acc_get: field elements parked in
+"""Build-time check of the accumulation-register file of msm_accumulate_steps.h (acc_set / acc_get: field elements parked in
 a[144 .. 255] by asm statements the compiler cannot see into).  Reads the assembly hipcc emits for the device
 (-save-temps: inline asm statements are bracketed by ;;#ASMSTART / ;;#ASMEND there -- a disassembly cannot tell the
 compiler's own v_accvgpr_write from acc_set's) and fails if, in any kernel whose asm statements touch the file, an

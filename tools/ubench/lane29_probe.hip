@@ -1,5 +1,5 @@
 // Limb-per-lane field / group arithmetic (csrc/lane29.h) against the one-product-per-lane chains it replaces
-// (msm_impl.h: dbl_wave29 / add_wave29): semantics of the row primitives on this device, parity of products and group
+// (msm_chains.h: dbl_wave29 / add_wave29): semantics of the row primitives on this device, parity of products and group
 // operations on random operands and on the special cases, and the time of a dependent chain in both forms.
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 -I distributed-groth16_amd/csrc -I include tools/ubench/lane29_probe.hip -o tools/ubench/lane29_probe
 #include "msm_impl.h"
