@@ -100,14 +100,50 @@ where
         Ok((a, b, c))
     }
 
+    /// The evaluation vectors of `LibsnarkReduction` (a = A w, b = B w, c = C w; ark-groth16's default witness map, which
+    /// the reference uses at ark-circom/src/zkey.rs:921) and the R1CS check fused into the same pass: `(violated rows,
+    /// first violated row)` -- `(0, None)` is `ConstraintSystem::is_satisfied`.
+    #[allow(clippy::type_complexity)]
+    pub fn qap_r1cs(&self, m: &ConstraintMatrices<E::ScalarField>, w: &[E::ScalarField])
+        -> Result<(Vec<E::ScalarField>, Vec<E::ScalarField>, Vec<E::ScalarField>, (u64, Option<u64>)), Dg16Error> {
+        let (ca, cb, cc) = (Csr::from_rows(&m.a), Csr::from_rows(&m.b), Csr::from_rows(&m.c));
+        let z = E::ScalarField::zero();
+        let (mut a, mut b, mut c) = (vec![z; self.domain_size], vec![z; self.domain_size], vec![z; self.domain_size]);
+        let mut viol = [0u64; 2];
+        check(unsafe {
+            sys::dg16_qap_r1cs(
+                CTX.0, self.curve, m.num_constraints, self.num_inputs, self.num_vars, self.domain_size.trailing_zeros(),
+                ca.row_ptr.as_ptr(), ca.col.as_ptr(), scalars_as_bytes(&ca.coeff).as_ptr().cast(),
+                cb.row_ptr.as_ptr(), cb.col.as_ptr(), scalars_as_bytes(&cb.coeff).as_ptr().cast(),
+                cc.row_ptr.as_ptr(), cc.col.as_ptr(), scalars_as_bytes(&cc.coeff).as_ptr().cast(),
+                scalars_as_bytes(w).as_ptr().cast(), 0, 1,
+                scalars_as_bytes_mut(&mut a).as_mut_ptr().cast(), scalars_as_bytes_mut(&mut b).as_mut_ptr().cast(),
+                scalars_as_bytes_mut(&mut c).as_mut_ptr().cast(), viol.as_mut_ptr(), sys::DG16_F_SCALARS_MONT, 0,
+            )
+        })?;
+        Ok((a, b, c, (viol[0], if viol[0] != 0 { Some(viol[1]) } else { None })))
+    }
+
+    /// `prove` for a key made with `LibsnarkReduction` (`Groth16::<E>`'s default): h = (A B - C) / Z of the a, b, c of
+    /// `qap_r1cs`.
+    pub fn prove_libsnark(&self, a: &[E::ScalarField], b: &[E::ScalarField], c: &[E::ScalarField],
+                          full_assignment: &[E::ScalarField], r: E::ScalarField, s: E::ScalarField)
+        -> Result<Proof<E>, Dg16Error> {
+        self.prove_with_flags(a, b, c, full_assignment, r, s, sys::DG16_F_SCALARS_MONT | sys::DG16_F_QAP_LIBSNARK)
+    }
+
     /// h-polynomial, five MSMs (A, B1, L, H in G1; B in G2), A / B / C assembly (groth16/src/prove.rs:21-136 for a
     /// single party).  Uses all three channels of the context.
     pub fn prove(&self, a: &[E::ScalarField], b: &[E::ScalarField], c: &[E::ScalarField], full_assignment: &[E::ScalarField],
                  r: E::ScalarField, s: E::ScalarField) -> Result<Proof<E>, Dg16Error> {
+        self.prove_with_flags(a, b, c, full_assignment, r, s, sys::DG16_F_SCALARS_MONT)
+    }
+
+    fn prove_with_flags(&self, a: &[E::ScalarField], b: &[E::ScalarField], c: &[E::ScalarField], full_assignment: &[E::ScalarField],
+                 r: E::ScalarField, s: E::ScalarField, flags: c_uint) -> Result<Proof<E>, Dg16Error> {
         let (f1, f2) = (<P1::BaseField as FieldBytes>::BYTES, <P2::BaseField as FieldBytes>::BYTES);
         let mut out = vec![0u8; 3 * f1 + 3 * f2 + 3 * f1];
         let rs = [r, s];
-        let flags: c_uint = sys::DG16_F_SCALARS_MONT;
         check(unsafe {
             sys::dg16_groth16_prove(
                 CTX.0, self.pk, scalars_as_bytes(a).as_ptr().cast(), scalars_as_bytes(b).as_ptr().cast(),

@@ -34,6 +34,7 @@ pub const DG16_F_H_CYCLIC: c_uint = 8;
 pub const DG16_F_SERIAL_CHANNELS: c_uint = 16;
 pub const DG16_F_OVERLAP_TAIL: c_uint = 32;
 pub const DG16_F_BASES_IN_SUBGROUP: c_uint = 64;
+pub const DG16_F_QAP_LIBSNARK: c_uint = 128;
 // enum dg16_field_opcode
 pub const DG16_OP_ADD: c_int = 0;
 pub const DG16_OP_SUB: c_int = 1;
@@ -180,6 +181,13 @@ extern "C" {
                     a_coeff: *const c_void, b_row_ptr: *const u32, b_col: *const u32, b_coeff: *const c_void,
                     full_assignment: *const c_void, row_start: usize, row_stride: usize, a_out: *mut c_void,
                     b_out: *mut c_void, c_out: *mut c_void, flags: c_uint, channel: c_int) -> c_int;
+    pub fn dg16_qap_r1cs(ctx: *mut Dg16Ctx, curve: c_int, num_constraints: usize, num_inputs: usize,
+                    num_vars: usize, log_m: c_uint, a_row_ptr: *const u32, a_col: *const u32,
+                    a_coeff: *const c_void, b_row_ptr: *const u32, b_col: *const u32, b_coeff: *const c_void,
+                    c_row_ptr: *const u32, c_col: *const u32, c_coeff: *const c_void,
+                    full_assignment: *const c_void, row_start: usize, row_stride: usize, a_out: *mut c_void,
+                    b_out: *mut c_void, c_out: *mut c_void, violations: *mut u64, flags: c_uint,
+                    channel: c_int) -> c_int;
     pub fn dg16_gen_bases(ctx: *mut Dg16Ctx, curve: c_int, group: c_int, seed: u64, n: usize, out: *mut c_void,
                           flags: c_uint, channel: c_int) -> c_int;
     // key generation: fixed-base batch multiplication, Groth16 setup (circuit_specific_setup)

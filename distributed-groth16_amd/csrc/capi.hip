@@ -108,6 +108,9 @@ void dg16_ctx_destroy(dg16_ctx* ctx) {
                     kv.second.full[0], kv.second.full[1], kv.second.shift_full})
       if (q) hipFree(q);
   }
+  for (auto& kv : ctx->cosets)
+    for (void* q : {kv.second.g_lo, kv.second.g_hi, kv.second.gi_lo, kv.second.gi_hi, kv.second.zg_inv})
+      if (q) hipFree(q);
   delete ctx;
 }
 
@@ -256,7 +259,8 @@ int dg16_h_poly(dg16_ctx* ctx, int curve, const void* a, const void* b, const vo
     const void* db = stage_in(k, 1, b, bytes, dev);
     const void* dc = stage_in(k, 2, c, bytes, dev);
     void* dout = dev ? out : ws(k.c, 3, bytes);
-    h_poly_launch(k, curve, da, db, dc, log_m, dout);
+    if (flags & DG16_F_QAP_LIBSNARK) h_poly_libsnark_launch(k, curve, da, db, dc, log_m, dout);
+    else h_poly_launch(k, curve, da, db, dc, log_m, dout);
     if (!dev) stage_out(k, out, dout, bytes, false);
     k.finish();
     if (!dev) DG_HIP(hipStreamSynchronize(k.s()));
@@ -468,6 +472,70 @@ int dg16_qap_rows(dg16_ctx* ctx, int curve, size_t num_constraints, size_t num_i
   });
 }
 
+// dg16_qap_rows with the C matrix (c = C w) and the fused R1CS check.
+int dg16_qap_r1cs(dg16_ctx* ctx, int curve, size_t num_constraints, size_t num_inputs, size_t num_vars, unsigned log_m,
+                  const uint32_t* a_row_ptr, const uint32_t* a_col, const void* a_coeff, const uint32_t* b_row_ptr,
+                  const uint32_t* b_col, const void* b_coeff, const uint32_t* c_row_ptr, const uint32_t* c_col,
+                  const void* c_coeff, const void* full_assignment, size_t row_start, size_t row_stride, void* a_out,
+                  void* b_out, void* c_out, uint64_t* violations, unsigned flags, int channel) {
+  int rc = guard_channel(ctx, channel);
+  if (rc) return rc;
+  return guarded(ctx, [&] {
+    DG_REQUIRE(curve >= 0 && curve <= 2, DG16_ERR_BAD_CURVE, "unknown curve id");
+    DG_REQUIRE(a_row_ptr && b_row_ptr && c_row_ptr && full_assignment && a_out && b_out && c_out, DG16_ERR_BAD_ARG,
+               "null operand");
+    DG_REQUIRE(log_m <= 30, DG16_ERR_BAD_ARG, "domain too large");
+    const size_t m = (size_t)1 << log_m;
+    DG_REQUIRE(row_stride >= 1 && !(row_stride & (row_stride - 1)) && row_stride <= m && row_start < row_stride,
+               DG16_ERR_BAD_ARG, "row_stride must be a power of two <= the domain, row_start < row_stride");
+    const size_t rows = m / row_stride;     // output elements per vector
+    DG_REQUIRE(num_constraints + num_inputs <= m && num_inputs <= num_vars, DG16_ERR_BAD_ARG,
+               "domain smaller than num_constraints + num_inputs");
+    const bool dev = flags & DG16_F_DEVICE_PTRS;
+    Call k(ctx, channel, /*tail_ok=*/dev);      // on device pointers this call touches no workspace (ctx.h: tail_pending)
+    // untrusted indices: the rules of dg16_qap_rows (host pointers checked here, device pointers by the kernel)
+    const uint32_t* rp[3] = {a_row_ptr, b_row_ptr, c_row_ptr};
+    const uint32_t* cl[3] = {a_col, b_col, c_col};
+    const void* cf[3] = {a_coeff, b_coeff, c_coeff};
+    size_t nnz[3] = {0, 0, 0};
+    if (!dev)
+      for (int j = 0; j < 3; j++) {
+        DG_REQUIRE(rp[j][0] == 0, DG16_ERR_BAD_ARG, "row_ptr[0] != 0");
+        for (size_t i = 0; i < num_constraints; i++)
+          DG_REQUIRE(rp[j][i] <= rp[j][i + 1], DG16_ERR_BAD_ARG, "row_ptr is not monotonic");
+        nnz[j] = rp[j][num_constraints];
+        DG_REQUIRE(nnz[j] == 0 || (cl[j] && cf[j]), DG16_ERR_BAD_ARG, "null column indices or coefficients");
+        for (size_t e = 0; e < nnz[j]; e++)
+          DG_REQUIRE(cl[j][e] < num_vars, DG16_ERR_BAD_ARG, "coefficient out of range (column >= num_vars)");
+      }
+    static const int slot_ptr[3] = {0, 3, 10}, slot_col[3] = {1, 18, 11}, slot_val[3] = {2, 19, 12};
+    const unsigned *dp[3], *dcl[3];
+    const void* dv[3];
+    for (int j = 0; j < 3; j++) {
+      dp[j] = (const unsigned*)stage_in(k, slot_ptr[j], rp[j], (num_constraints + 1) * 4, dev);
+      dcl[j] = (const unsigned*)stage_in(k, slot_col[j], cl[j], nnz[j] * 4, dev);
+      dv[j] = stage_in(k, slot_val[j], cf[j], nnz[j] * 32, dev);
+    }
+    const void* w = stage_in(k, 20, full_assignment, num_vars * 32, dev);
+    uint8_t* out = dev ? nullptr : (uint8_t*)ws(k.c, 21, 3 * rows * 32);
+    void* da = dev ? a_out : out;
+    void* db = dev ? b_out : out + rows * 32;
+    void* dc = dev ? c_out : out + 2 * rows * 32;
+    unsigned long long* dviol = !violations ? nullptr : dev ? (unsigned long long*)violations
+                                                            : (unsigned long long*)ws(k.c, 13, 16);
+    qap_r1cs_launch(k, curve, dp, dcl, dv, w, flags & DG16_F_SCALARS_MONT, num_constraints, num_inputs, num_vars, m,
+                    row_start, row_stride, da, db, dc, dviol);
+    if (!dev) {
+      stage_out(k, a_out, da, rows * 32, false);
+      stage_out(k, b_out, db, rows * 32, false);
+      stage_out(k, c_out, dc, rows * 32, false);
+      if (violations) stage_out(k, violations, dviol, 16, false);
+    }
+    k.finish();
+    if (!dev) DG_HIP(hipStreamSynchronize(k.s()));
+  });
+}
+
 
 int dg16_ntt_dist_stage(dg16_ctx* ctx, int curve, unsigned log_n, unsigned rank, unsigned n_ranks, int inverse,
                         int stage, const void* in, void* out, unsigned flags, int channel) {
@@ -513,6 +581,8 @@ int dg16_h_poly_dist_stage(dg16_ctx* ctx, int curve, unsigned log_m, unsigned ra
   return guarded(ctx, [&] {
     DG_REQUIRE(curve >= 0 && curve <= 2, DG16_ERR_BAD_CURVE, "unknown curve id");
     DG_REQUIRE(flags & DG16_F_DEVICE_PTRS, DG16_ERR_BAD_ARG, "the sharded h-polynomial works on device buffers");
+    DG_REQUIRE(!(flags & DG16_F_QAP_LIBSNARK), DG16_ERR_UNSUPPORTED,
+               "DG16_F_QAP_LIBSNARK: the sharded h-polynomial is the circom reduction's only");
     DG_REQUIRE(in && in[0] && out && stage >= 0 && stage <= 2 && (stage != 0 || (in[1] && in[2])), DG16_ERR_BAD_ARG,
                "null operand or unknown stage");
     Call k(ctx, channel);
@@ -530,6 +600,8 @@ int dg16_h_poly_dist(dg16_ctx* ctx, int curve, const dg16_comm* comm, const void
   return guarded(ctx, [&] {
     DG_REQUIRE(curve >= 0 && curve <= 2, DG16_ERR_BAD_CURVE, "unknown curve id");
     DG_REQUIRE(flags & DG16_F_DEVICE_PTRS, DG16_ERR_BAD_ARG, "the sharded h-polynomial works on device buffers");
+    DG_REQUIRE(!(flags & DG16_F_QAP_LIBSNARK), DG16_ERR_UNSUPPORTED,
+               "DG16_F_QAP_LIBSNARK: the sharded h-polynomial is the circom reduction's only");
     DG_REQUIRE(a_rows && b_rows && c_rows && out, DG16_ERR_BAD_ARG, "null operand");
     Call k(ctx, channel);
     k.begin_dominant();

@@ -10,6 +10,7 @@
 #include <atomic>
 #include <mutex>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "../../include/dg16.h"
@@ -55,6 +56,14 @@ struct TwiddleSet {   // all device pointers, 32-byte Fr elements
   void* shift_full = nullptr;
   bool shift_full_tried = false;   // the optional table's allocation is attempted once per cache entry
 };
+// Libsnark h-polynomial (qap_libsnark.hip): the power tables of the coset offset g = F::GENERATOR -- not a root of unity,
+// so not a twiddle set -- in the split lo x hi internal form the NTT passes multiply by, built once per (curve, log_m)
+struct CosetSet {
+  void *g_lo = nullptr, *g_hi = nullptr;      // g^j, j < 2^lb | g^(j << lb)
+  void *gi_lo = nullptr, *gi_hi = nullptr;    // the same for g^-1
+  void* zg_inv = nullptr;                     // 1 / (g^m - 1), arkworks Montgomery form (one element)
+  unsigned lb = 0;
+};
 
 }  // namespace dg16
 
@@ -89,6 +98,7 @@ struct dg16_ctx {
   // 0 = unlimited (one table row per window)
   size_t table_budget = 0;
   std::map<dg16::TwiddleKey, dg16::TwiddleSet> twiddles;
+  std::map<std::pair<int, unsigned>, dg16::CosetSet> cosets;   // (curve, log_m); guarded by mu like the twiddles
 };
 
 struct dg16_bases {          // resident bases: table of window multiples (dg16_bases_upload)
@@ -226,6 +236,17 @@ void ntt_dist_launch(Call& k, int curve, const dg16_comm* comm, const void* in, 
 void ntt_launch(Call& k, int curve, void* data, unsigned log_n, int inverse, const void* coset_host);
 void h_poly_launch(Call& k, int curve, const void* a, const void* b, const void* c, unsigned log_m,
                    void* out);
+// qap_libsnark.hip: the Libsnark flavour (DG16_F_QAP_LIBSNARK) of the two calls above it mirrors
+void qap_r1cs_launch(Call& k, int curve, const unsigned* const* row_ptr, const unsigned* const* col, const void* const* val,
+                     const void* w, bool w_mont, size_t nc, size_t ni, size_t nv, size_t m, size_t row_start,
+                     size_t row_stride, void* a, void* b, void* c, unsigned long long* violations);
+void h_poly_libsnark_launch(Call& k, int curve, const void* a, const void* b, const void* c, unsigned log_m, void* out);
+// ntt.hip, for compositions outside it: nb <= 3 transforms through the launches dg16_ntt uses (pre_* / post_*: split
+// power tables in the internal form, or null), and such tables for an arbitrary base
+void ntt_batch_launch(Call& k, int curve, unsigned nb, const void* const* in, void* const* data, void* const* tmp,
+                      unsigned log_n, int inverse, const void* pre_lo, const void* pre_hi, const void* post_lo,
+                      const void* post_hi, unsigned plb);
+void power_tables_launch(Call& k, int curve, const void* base_dev, unsigned log_n, void* lo, void* hi, unsigned lb);
 bool net_is_rccl(const dg16_net* net);     // rccl_net.hip: the library's own RCCL transport
 // `mode` of the plain-MSM entry points: bit 0 = scalars in Montgomery form, bit 1 = DG16_F_BASES_IN_SUBGROUP
 inline unsigned msm_mode(unsigned flags) {

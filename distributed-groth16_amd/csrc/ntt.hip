@@ -960,6 +960,31 @@ void h_poly_dist_launch(Call& k, int curve, const dg16_comm* comm, const void* a
   h_poly_dist_stage(k, curve, log_m, rank, n, 2, in1, out);
 }
 
+// the batch runner and the power tables for compositions outside this file (qap_libsnark.hip)
+template <class F>
+static void ntt_batch_typed(Call& k, int curve, unsigned nb, const void* const* in, void* const* data, void* const* tmp,
+                            unsigned log_n, int inverse, const void* pre_lo, const void* pre_hi, const void* post_lo,
+                            const void* post_hi, unsigned plb) {
+  ntt_run_batch<F>(k, curve, nb, (const F* const*)in, (F* const*)data, (F* const*)tmp, log_n, inverse, (const F*)pre_lo,
+                   (const F*)pre_hi, (const F*)post_lo, (const F*)post_hi, plb);
+}
+void ntt_batch_launch(Call& k, int curve, unsigned nb, const void* const* in, void* const* data, void* const* tmp,
+                      unsigned log_n, int inverse, const void* pre_lo, const void* pre_hi, const void* post_lo,
+                      const void* post_hi, unsigned plb) {
+  switch (curve) {
+    case 0: ntt_batch_typed<bn254_fr>(k, curve, nb, in, data, tmp, log_n, inverse, pre_lo, pre_hi, post_lo, post_hi, plb); break;
+    case 1: ntt_batch_typed<bls12_381_fr>(k, curve, nb, in, data, tmp, log_n, inverse, pre_lo, pre_hi, post_lo, post_hi, plb); break;
+    default: ntt_batch_typed<bls12_377_fr>(k, curve, nb, in, data, tmp, log_n, inverse, pre_lo, pre_hi, post_lo, post_hi, plb); break;
+  }
+}
+void power_tables_launch(Call& k, int curve, const void* base_dev, unsigned log_n, void* lo, void* hi, unsigned lb) {
+  switch (curve) {
+    case 0: build_power_tables<bn254_fr>(k, (const bn254_fr*)base_dev, log_n, (bn254_fr*)lo, (bn254_fr*)hi, lb); break;
+    case 1: build_power_tables<bls12_381_fr>(k, (const bls12_381_fr*)base_dev, log_n, (bls12_381_fr*)lo, (bls12_381_fr*)hi, lb); break;
+    default: build_power_tables<bls12_377_fr>(k, (const bls12_377_fr*)base_dev, log_n, (bls12_377_fr*)lo, (bls12_377_fr*)hi, lb); break;
+  }
+}
+
 void h_poly_launch(Call& k, int curve, const void* a, const void* b, const void* c, unsigned log_m, void* out) {
   switch (curve) {
     case 0: h_poly_typed<bn254_fr>(k, curve, a, b, c, log_m, out); break;

@@ -8,7 +8,7 @@ namespace dg16 {
 #define DECL_P(name)                                                                                                   \
   void pk_build_##name(dg16_ctx*, PkDev&, const void*, const void*, const void*, const void*, const void*, const void*, bool); \
   void prove_##name(dg16_ctx*, const PkDev&, const void*, const void*, const void*, const void*, const void*, bool, bool, void*, \
-                    bool); \
+                    bool, bool); \
   void msms_##name(dg16_ctx*, Call&, Call&, Call&, const PkDev&, const void*, const void*, const void*, const void*,    \
                    const void*, bool, bool, uint8_t*, const dg16_comm*, const void*);                                   \
   void prove_dist_##name(dg16_ctx*, const PkDev&, const dg16_comm*, const void*, const void*, const void*, const void*, \
@@ -101,10 +101,11 @@ int dg16_groth16_prove(dg16_ctx* ctx, const dg16_pk* pk, const void* a, const vo
     DG_REQUIRE(a && b && c && full_assignment && r_s && proof_out, DG16_ERR_BAD_ARG, "null operand");
     bool mont = flags & DG16_F_SCALARS_MONT, dev = flags & DG16_F_DEVICE_PTRS;
     const bool overlap = (flags & DG16_F_OVERLAP_TAIL) && dev;
+    const bool libsnark = flags & DG16_F_QAP_LIBSNARK;
     if (pk->d.curve == DG16_BN254)
-      prove_bn254(ctx, pk->d, a, b, c, full_assignment, r_s, mont, dev, proof_out, overlap);
+      prove_bn254(ctx, pk->d, a, b, c, full_assignment, r_s, mont, dev, proof_out, overlap, libsnark);
     else
-      prove_bls12_381(ctx, pk->d, a, b, c, full_assignment, r_s, mont, dev, proof_out, overlap);
+      prove_bls12_381(ctx, pk->d, a, b, c, full_assignment, r_s, mont, dev, proof_out, overlap, libsnark);
   });
 }
 
@@ -117,6 +118,8 @@ int dg16_groth16_msms(dg16_ctx* ctx, const dg16_pk* pk, const void* a, const voi
   if (!ctx || !pk) return DG16_ERR_BAD_ARG;
   return guarded(ctx, [&] {
     DG_REQUIRE(pk->ctx == ctx, DG16_ERR_BAD_ARG, "proving key belongs to another context");
+    DG_REQUIRE(!(flags & DG16_F_QAP_LIBSNARK), DG16_ERR_UNSUPPORTED,
+               "DG16_F_QAP_LIBSNARK: the sharded entry points prove with the circom reduction only");
     DG_REQUIRE(a && b && c && full_assignment && r_s && results_out, DG16_ERR_BAD_ARG, "null operand");
     bool mont = flags & DG16_F_SCALARS_MONT, dev = flags & DG16_F_DEVICE_PTRS;
     Call k0(ctx, 0), k1(ctx, 1), k2(ctx, 2);
@@ -141,6 +144,8 @@ int dg16_groth16_msms_h(dg16_ctx* ctx, const dg16_pk* pk, const void* h_shard, c
   if (!ctx || !pk) return DG16_ERR_BAD_ARG;
   return guarded(ctx, [&] {
     DG_REQUIRE(pk->ctx == ctx, DG16_ERR_BAD_ARG, "proving key belongs to another context");
+    DG_REQUIRE(!(flags & DG16_F_QAP_LIBSNARK), DG16_ERR_UNSUPPORTED,
+               "DG16_F_QAP_LIBSNARK: the sharded entry points prove with the circom reduction only");
     DG_REQUIRE(h_shard && full_assignment && r_s && results_out, DG16_ERR_BAD_ARG, "null operand");
     bool mont = flags & DG16_F_SCALARS_MONT, dev = flags & DG16_F_DEVICE_PTRS;
     Call k0(ctx, 0), k1(ctx, 1), k2(ctx, 2);
@@ -167,6 +172,8 @@ int dg16_groth16_prove_dist(dg16_ctx* ctx, const dg16_pk* pk, const dg16_comm* c
   if (!ctx || !pk) return DG16_ERR_BAD_ARG;
   return guarded(ctx, [&] {
     DG_REQUIRE(pk->ctx == ctx, DG16_ERR_BAD_ARG, "proving key belongs to another context");
+    DG_REQUIRE(!(flags & DG16_F_QAP_LIBSNARK), DG16_ERR_UNSUPPORTED,
+               "DG16_F_QAP_LIBSNARK: the sharded entry points prove with the circom reduction only");
     DG_REQUIRE(a_rows && b_rows && c_rows && full_assignment && r_s && proof_out, DG16_ERR_BAD_ARG, "null operand");
     bool mont = flags & DG16_F_SCALARS_MONT, dev = flags & DG16_F_DEVICE_PTRS;
     const bool overlap = (flags & DG16_F_OVERLAP_TAIL) && dev;

@@ -268,7 +268,8 @@ static size_t msm_results_bytes() {
 //   h_given            the caller made it (this key's n_h scalars; a, b, c unused)
 //   comm with > 1 rank  sharded h-polynomial (ntt.hip: h_poly_dist_launch): a, b, c are this rank's cyclic rows and
 //                      the key is a DG16_F_H_CYCLIC shard
-//   otherwise          the whole h-polynomial from the whole a, b, c; the key's slice of it is used
+//   otherwise          the whole h-polynomial from the whole a, b, c; the key's slice of it is used (libsnark_h: the
+//                      Libsnark quotient of qap_libsnark.hip instead of the circom witness map)
 // overlap_tail (DG16_F_OVERLAP_TAIL, one GPU): H's bucket reduction -- the exposed tail of a proof, ~0.6 ms of latency-bound
 // launches on an otherwise idle chip -- goes down channel 2's stream instead of channel 0's, so that what the caller
 // enqueues next on channel 0 (the next proof's R1CS x witness and h-polynomial) runs under it.  Returns true when it did:
@@ -280,7 +281,7 @@ template <int CURVE>
 static bool msms_typed(dg16_ctx* ctx, Call& k0, Call& k1, Call& k2, const PkDev& pk, const void* a, const void* b,
                        const void* c, const void* witness, const void* r_s_host, bool mont, bool dev_ptrs,
                        uint8_t* res_dev, const dg16_comm* comm = nullptr, const void* h_given = nullptr,
-                       bool overlap_tail = false) {
+                       bool overlap_tail = false, bool libsnark_h = false) {
   using CT = CurveTypes<CURVE>;
   using Fq = typename CT::Fq;
   using Fq2 = typename CT::Fq2;
@@ -379,7 +380,9 @@ static bool msms_typed(dg16_ctx* ctx, Call& k0, Call& k1, Call& k2, const PkDev&
   Fr* h_dev = h_given ? nullptr : (Fr*)ws(k0.c, 3, rows * sizeof(Fr));
   const Fr* h_scalars = h_in;
   auto whole_h = [&] {
-    h_poly_launch(k0, CURVE, a_dev, b_dev, c_dev, log_m, h_dev);
+    // (DG16_F_QAP_LIBSNARK: the quotient (A B - C) / Z -- same stream, same workspace slots, same output)
+    if (libsnark_h) h_poly_libsnark_launch(k0, CURVE, a_dev, b_dev, c_dev, log_m, h_dev);
+    else h_poly_launch(k0, CURVE, a_dev, b_dev, c_dev, log_m, h_dev);
     h_scalars = h_dev + pk.h_lo;
   };
   const hipStream_t pro = queued ? side : main;      // the prologue's stream
@@ -575,7 +578,7 @@ static void assemble_typed(Call& k0, const uint8_t* gathered_dev, size_t n_shard
 template <int CURVE>
 static void prove_typed(dg16_ctx* ctx, const PkDev& pk, const void* a, const void* b, const void* c,
                         const void* witness, const void* r_s_host, bool mont, bool dev_ptrs, void* proof_out,
-                        bool overlap_tail = false) {
+                        bool overlap_tail = false, bool libsnark_h = false) {
   using CT = CurveTypes<CURVE>;
   const size_t g1j = sizeof(Jacobian<typename CT::Fq>), g2j = sizeof(Jacobian<typename CT::Fq2>);
   DG_REQUIRE(pk.nshards == 1, DG16_ERR_BAD_ARG, "dg16_groth16_prove needs an unsharded key; use _msms + _assemble");
@@ -586,7 +589,7 @@ static void prove_typed(dg16_ctx* ctx, const PkDev& pk, const void* a, const voi
   uint8_t* proof_dev = buf + 4096;
   k0.begin_dominant();
   const bool tail = msms_typed<CURVE>(ctx, k0, k1, k2, pk, a, b, c, witness, r_s_host, mont, dev_ptrs, res_dev, nullptr,
-                                      nullptr, overlap_tail);
+                                      nullptr, overlap_tail, libsnark_h);
   if (tail) {
     // the proof is complete on channel 2's stream (dg16.h: DG16_F_OVERLAP_TAIL); channel 0 is free for the next one
     k0.end_dominant();

@@ -13,6 +13,7 @@ struct SetupArgs {
   size_t nnz[3];
   const void* trapdoor;                     // host: alpha | beta | gamma | delta | tau, canonical
   const void* generators;                   // host: g1 affine | g2 affine, or null
+  bool libsnark;                            // DG16_F_QAP_LIBSNARK: h_query = [tau^i Z(tau) / delta]_{i < m-1} | identity
   // device outputs
   void *a_query, *b_g1_query, *b_g2_query, *h_query, *l_query, *fixed_points, *gamma_g2, *gamma_abc_g1;
 };

@@ -76,6 +76,7 @@ int dg16_groth16_setup(dg16_ctx* ctx, int curve, size_t num_constraints, size_t 
     s.nc = nc; s.ni = ni; s.nv = nv; s.log_m = log_m;
     s.trapdoor = trapdoor;
     s.generators = generators;
+    s.libsnark = flags & DG16_F_QAP_LIBSNARK;
     const uint32_t* rp[3] = {a_row_ptr, b_row_ptr, c_row_ptr};
     const uint32_t* cl[3] = {a_col, b_col, c_col};
     const void* cf[3] = {a_coeff, b_coeff, c_coeff};

@@ -7,6 +7,7 @@
 //                              scan, fill); one lane per wire then GATHERS its column -- there is no atomic add in Fr
 //   abc_k = beta a_k + alpha b_k + c_k, / gamma for the instance wires, / delta for the witness wires
 //   h                          inverse NTT of size 2 m of [tau^j / delta]_{j < 2m-1} | 0, odd-indexed entries
+//                              (DG16_F_QAP_LIBSNARK: the geometric sequence tau^i Z(tau) / delta, i < m - 1, then 0)
 //   seven fixed-base calls     a, b (G1), b (G2), h, l, gamma_abc, and the six fixed points
 #include <string.h>
 
@@ -38,6 +39,21 @@ __global__ void __launch_bounds__(256) setup_powers_kernel(Fr* __restrict__ out,
   size_t j = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (j >= total) return;
   out[j] = j < count ? base->pow_u64((uint64_t)j) * *scale : Fr::zero();
+}
+
+// out[j] = scale * base^j for j < count, zero for count <= j < total, as a chunked power ladder: a lane raises base to
+// the start of its kGeoChunk consecutive exponents once (log2 steps) and multiplies its way through them
+constexpr unsigned kGeoChunk = 16;
+__global__ void __launch_bounds__(256) setup_geometric_kernel(Fr* __restrict__ out, size_t count, size_t total,
+                                                               const Fr* __restrict__ base, const Fr* __restrict__ scale) {
+  const size_t j0 = ((size_t)blockIdx.x * blockDim.x + threadIdx.x) * kGeoChunk;
+  if (j0 >= total) return;
+  const Fr g = *base;
+  Fr v = j0 < count ? g.pow_u64((uint64_t)j0) * *scale : Fr::zero();
+  for (size_t j = j0; j < j0 + kGeoChunk && j < total; j++) {
+    out[j] = j < count ? v : Fr::zero();
+    v = v * g;
+  }
 }
 
 __global__ void __launch_bounds__(256) setup_odd_kernel(const Fr* __restrict__ in, size_t m, Fr* __restrict__ out) {
@@ -174,10 +190,12 @@ void groth16_setup_run<DG_CURVE>(Call& k, const SetupArgs& s) {
   DG_REQUIRE(zt != Fr::one(), DG16_ERR_BAD_ARG, "tau lies in the evaluation domain (tau^m = 1)");
   const Fr dinv = delta.inv(), ginv = gamma.inv();
   // device constants: 0 alpha | 1 beta | 2 1/gamma | 3 1/delta | 4 tau | 5 one | 6..8 alpha beta delta | 9..11 beta delta gamma
-  const Fr host_consts[12] = {alpha, beta, ginv, dinv, tau, Fr::one(), alpha, beta, delta, beta, delta, gamma};
+  //                   12 Z(tau) / delta
+  const Fr host_consts[13] = {alpha, beta, ginv, dinv, tau, Fr::one(), alpha, beta, delta, beta, delta, gamma,
+                              (zt - Fr::one()) * dinv};
   DevBuf consts(sizeof host_consts + 16);
   Fr* cd = consts.as<Fr>();
-  unsigned* flag = (unsigned*)(cd + 12);
+  unsigned* flag = (unsigned*)(cd + 13);
   DG_HIP(hipMemcpyAsync(cd, host_consts, sizeof host_consts, hipMemcpyHostToDevice, k.s()));
   DG_HIP(hipMemsetAsync(flag, 0, 16, k.s()));
   DG_HIP(hipStreamSynchronize(k.s()));          // host_consts is a stack buffer
@@ -191,15 +209,21 @@ void groth16_setup_run<DG_CURVE>(Call& k, const SetupArgs& s) {
   DevBuf a_s(nv * sizeof(Fr)), b_s(nv * sizeof(Fr)), gabc_s(ni * sizeof(Fr)), l_s((nv - ni) * sizeof(Fr)),
       h_s(m * sizeof(Fr));
   {
-    DevBuf u(m * sizeof(Fr)), big(2 * m * sizeof(Fr));
+    DevBuf u(m * sizeof(Fr)), big(s.libsnark ? 0 : 2 * m * sizeof(Fr));
     hipLaunchKernelGGL(setup_powers_kernel, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, k.s(), u.as<Fr>(), m, m,
                        cd + 4, cd + 5);
     ntt_launch(k, DG_CURVE, u.p, s.log_m, 1, nullptr);
-    hipLaunchKernelGGL(setup_powers_kernel, dim3((unsigned)((2 * m + 255) / 256)), dim3(256), 0, k.s(), big.as<Fr>(),
-                       2 * m - 1, 2 * m, cd + 4, cd + 3);
-    ntt_launch(k, DG_CURVE, big.p, s.log_m + 1, 1, nullptr);
-    hipLaunchKernelGGL(setup_odd_kernel, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, k.s(), big.as<Fr>(), m,
-                       h_s.as<Fr>());
+    if (s.libsnark) {
+      const size_t lanes = (m + kGeoChunk - 1) / kGeoChunk;
+      hipLaunchKernelGGL(setup_geometric_kernel, dim3((unsigned)((lanes + 255) / 256)), dim3(256), 0, k.s(), h_s.as<Fr>(),
+                         m - 1, m, cd + 4, cd + 12);
+    } else {
+      hipLaunchKernelGGL(setup_powers_kernel, dim3((unsigned)((2 * m + 255) / 256)), dim3(256), 0, k.s(), big.as<Fr>(),
+                         2 * m - 1, 2 * m, cd + 4, cd + 3);
+      ntt_launch(k, DG_CURVE, big.p, s.log_m + 1, 1, nullptr);
+      hipLaunchKernelGGL(setup_odd_kernel, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, k.s(), big.as<Fr>(), m,
+                         h_s.as<Fr>());
+    }
     // transposes: per matrix ptr[nv + 1], cursor / counts [nv], t_row, t_src [nnz]
     DevBuf counts(3 * nv * sizeof(unsigned)), cursor(3 * nv * sizeof(unsigned)), ptr(3 * (nv + 1) * sizeof(unsigned));
     DevBuf trow((s.nnz[0] + s.nnz[1] + s.nnz[2]) * sizeof(unsigned)), tsrc((s.nnz[0] + s.nnz[1] + s.nnz[2]) * sizeof(unsigned));

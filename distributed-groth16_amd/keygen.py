@@ -129,9 +129,12 @@ class Parameters:
             self.host("gamma_abc_g1")
 
 
-def generate_parameters(ctx, curve, r1cs, trapdoor=None, generators=None):
+def generate_parameters(ctx, curve, r1cs, trapdoor=None, generators=None, reduction="circom"):
     """ctx: a Context (None: one is made on device 0 -- without a GPU that raises Dg16Error, there is no CPU path).
-    generators: None, or (g1 affine, g2 affine) as uint64 arrays.  Returns Parameters."""
+    generators: None, or (g1 affine, g2 affine) as uint64 arrays.  reduction: "circom" (CircomReduction, the snarkjs
+    h_query) or "libsnark" (ark-groth16's default LibsnarkReduction: h_query[i] = tau^i Z(tau) / delta, the last entry
+    the identity); prove with the same reduction.  Returns Parameters."""
+    _lib._reduction_flag(reduction)
     p = prepare(curve, r1cs, trapdoor)
     if ctx is None:
         ctx = _lib.Context(0)
@@ -169,5 +172,7 @@ def generate_parameters(ctx, curve, r1cs, trapdoor=None, generators=None):
     torch.cuda.synchronize(dev)        # the uploads ran on torch's stream, the generator runs on the library's
     ctx.sync(0)
     ctx.groth16_setup(curve, nc, ni, nv, log_m, *[[t.data_ptr() for t in m] for m in mats], p["trapdoor"],
-                      [t.data_ptr() for t in arrays], generators=gens, device_ptrs=True)
-    return Parameters(curve, nc, ni, nv, log_m, arrays, trapdoor=tuple(trapdoor) if p["trapdoor_given"] else None)
+                      [t.data_ptr() for t in arrays], generators=gens, device_ptrs=True, reduction=reduction)
+    params = Parameters(curve, nc, ni, nv, log_m, arrays, trapdoor=tuple(trapdoor) if p["trapdoor_given"] else None)
+    params.reduction = reduction
+    return params

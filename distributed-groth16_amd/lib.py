@@ -22,6 +22,17 @@ F_H_CYCLIC = 8
 F_SERIAL_CHANNELS = 16
 F_OVERLAP_TAIL = 32
 F_BASES_IN_SUBGROUP = 64
+F_QAP_LIBSNARK = 128
+
+REDUCTIONS = {"circom": 0, "libsnark": F_QAP_LIBSNARK}
+
+
+def _reduction_flag(reduction):
+    """"circom" (the snarkjs witness map, the default) or "libsnark" (ark-groth16's default LibsnarkReduction)."""
+    try:
+        return REDUCTIONS[reduction]
+    except KeyError:
+        raise ValueError("reduction must be 'circom' or 'libsnark', not %r" % (reduction,)) from None
 
 STATUS = {1: "LENGTH_MISMATCH", 2: "BAD_CURVE", 3: "BAD_ARG", 4: "OOM", 5: "HIP", 6: "NET",
           7: "UNSUPPORTED"}
@@ -162,6 +173,7 @@ def load():
     L.dg16_groth16_assemble.argtypes = [vp, vp, vp, sz, vp, u, vp]
     L.dg16_qap.argtypes = [vp, i, sz, sz, sz, u, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, u, i]
     L.dg16_qap_rows.argtypes = [vp, i, sz, sz, sz, u, vp, vp, vp, vp, vp, vp, vp, sz, sz, vp, vp, vp, u, i]
+    L.dg16_qap_r1cs.argtypes = [vp, i, sz, sz, sz, u] + [vp] * 10 + [sz, sz, vp, vp, vp, vp, u, i]
     L.dg16_h_poly_dist.argtypes = [vp, i, vp, vp, vp, vp, u, vp, u, i]
     L.dg16_ntt_dist.argtypes = [vp, i, vp, vp, vp, u, i, u, i]
     L.dg16_ntt_dist_stage.argtypes = [vp, i, u, u, u, i, i, vp, vp, u, i]
@@ -250,7 +262,7 @@ EXPORTED = ["dg16_ctx_create", "dg16_ctx_destroy", "dg16_last_error", "dg16_set_
             "dg16_groth16_assemble", "dg16_localnet_create", "dg16_localnet_party", "dg16_localnet_destroy", "dg16_localnet_abort",
             "dg16_localnet_reset",
             "dg16_pss_create", "dg16_pss_destroy", "dg16_pss_apply", "dg16_pss_apply_exp", "dg16_d_fft",
-            "dg16_d_msm", "dg16_deg_red", "dg16_d_pp", "dg16_ext_wit_h", "dg16_qap", "dg16_qap_rows",
+            "dg16_d_msm", "dg16_deg_red", "dg16_d_pp", "dg16_ext_wit_h", "dg16_qap", "dg16_qap_rows", "dg16_qap_r1cs",
             "dg16_h_poly_dist", "dg16_h_poly_dist_stage", "dg16_ntt_dist", "dg16_ntt_dist_stage", "dg16_groth16_msms_h", "dg16_groth16_prove_dist",
             "dg16_rccl_unique_id", "dg16_rccl_create", "dg16_rccl_comm", "dg16_rccl_net", "dg16_rccl_destroy", "dg16_rccl_ranks",
             "dg16_rccl_channels_split",
@@ -398,15 +410,16 @@ class Context:
         self._chk(self.L.dg16_ntt(self.h, CURVES[curve], _ptr(data), log_n, int(inverse), _ptr(coset), 0, channel))
         return data
 
-    def h_poly(self, curve, a, b, c, channel=0):
+    def h_poly(self, curve, a, b, c, channel=0, reduction="circom"):
+        """reduction="libsnark": the m coefficients of (A B - C) / Z instead of the circom witness map."""
         a, b, c = (np.ascontiguousarray(v, dtype=np.uint64) for v in (a, b, c))
         m = a.shape[0]
         log_m = m.bit_length() - 1
         if (1 << log_m) != m or b.shape != a.shape or c.shape != a.shape:
             raise ValueError("a, b, c must have equal power-of-two length")
         out = np.empty_like(a)
-        self._chk(self.L.dg16_h_poly(self.h, CURVES[curve], _ptr(a), _ptr(b), _ptr(c), log_m, _ptr(out), 0,
-                                     channel))
+        self._chk(self.L.dg16_h_poly(self.h, CURVES[curve], _ptr(a), _ptr(b), _ptr(c), log_m, _ptr(out),
+                                     _reduction_flag(reduction), channel))
         return out
 
     def msm(self, curve, group, bases, scalars, scalars_mont=False, affine=False, channel=0, in_subgroup=False):
@@ -518,11 +531,11 @@ class Context:
                                              channel))
 
     def groth16_setup(self, curve, num_constraints, num_inputs, num_vars, log_m, csr_a, csr_b, csr_c, trapdoor,
-                      outputs, generators=None, device_ptrs=False):
+                      outputs, generators=None, device_ptrs=False, reduction="circom"):
         """dg16_groth16_setup.  csr_* = (row_ptr, col, coeff): numpy arrays (coeff uint64 [nnz][4], Montgomery form) or
         raw device pointers with device_ptrs; trapdoor: uint64 [5][4] canonical (host); generators: host array g1 | g2 or
         None; outputs: the eight arrays / device pointers a_query, b_g1_query, b_g2_query, h_query, l_query,
-        fixed_points, gamma_g2, gamma_abc_g1.  Synchronous."""
+        fixed_points, gamma_g2, gamma_abc_g1.  reduction="libsnark": h_query of a LibsnarkReduction key.  Synchronous."""
         trapdoor = np.ascontiguousarray(trapdoor, dtype=np.uint64)
         generators = None if generators is None else np.ascontiguousarray(generators, dtype=np.uint64)
         mats = []
@@ -531,7 +544,8 @@ class Context:
         keep = (trapdoor, generators, mats)          # noqa: F841 (the arrays outlive the call)
         self._chk(self.L.dg16_groth16_setup(self.h, CURVES[curve], num_constraints, num_inputs, num_vars, log_m,
                                             *[_ptr(x) for x in mats], _ptr(trapdoor), _ptr(generators),
-                                            *[_ptr(x) for x in outputs], F_DEVICE_PTRS if device_ptrs else 0))
+                                            *[_ptr(x) for x in outputs],
+                                            (F_DEVICE_PTRS if device_ptrs else 0) | _reduction_flag(reduction)))
 
     def to_affine(self, curve, group, jac, channel=0):
         jac = np.ascontiguousarray(jac, dtype=np.uint64)
@@ -572,6 +586,31 @@ class Context:
                                        _ptr(a_ptr_p), _ptr(a_col_p), _ptr(a_val_p), _ptr(b_ptr_p), _ptr(b_col_p),
                                        _ptr(b_val_p), _ptr(w_p), row_start, row_stride, _ptr(a_out), _ptr(b_out),
                                        _ptr(c_out), F_DEVICE_PTRS | (F_SCALARS_MONT if scalars_mont else 0), channel))
+
+    def qap_r1cs(self, curve, num_constraints, num_inputs, csr_a, csr_b, csr_c, full_assignment, scalars_mont=True,
+                 channel=0, row_start=0, row_stride=1):
+        """dg16_qap_r1cs on host arrays: csr_* as for qap.  Returns (a, b, c, (n_violated, first_row | None))."""
+        w = np.ascontiguousarray(full_assignment, dtype=np.uint64).reshape(-1, 4)
+        log_m = max(num_constraints + num_inputs - 1, 0).bit_length()
+        rows = (1 << log_m) // row_stride
+        out = [np.zeros((rows, 4), dtype=np.uint64) for _ in range(3)]
+        viol = np.zeros(2, dtype=np.uint64)
+        mats = [np.ascontiguousarray(x) for m in (csr_a, csr_b, csr_c) for x in m]
+        self._chk(self.L.dg16_qap_r1cs(self.h, CURVES[curve], num_constraints, num_inputs, w.shape[0], log_m,
+                                       *[_ptr(x) for x in mats], _ptr(w), row_start, row_stride, _ptr(out[0]),
+                                       _ptr(out[1]), _ptr(out[2]), _ptr(viol), F_SCALARS_MONT if scalars_mont else 0,
+                                       channel))
+        n = int(viol[0])
+        return out[0], out[1], out[2], (n, int(viol[1]) if n else None)
+
+    def qap_r1cs_dev(self, curve, num_constraints, num_inputs, num_vars, log_m, csr_ptrs, w_p, a_out, b_out, c_out,
+                     violations_ptr=None, row_start=0, row_stride=1, scalars_mont=True, channel=0):
+        """Device pointers throughout (csr_ptrs: the nine pointers a_row_ptr, a_col, a_coeff, b_..., c_...); stream-ordered
+        on the channel.  violations_ptr: None, or two uint64 on the device (count, first violated row or 2^64 - 1)."""
+        self._chk(self.L.dg16_qap_r1cs(self.h, CURVES[curve], num_constraints, num_inputs, num_vars, log_m,
+                                       *[_ptr(x) for x in csr_ptrs], _ptr(w_p), row_start, row_stride, _ptr(a_out),
+                                       _ptr(b_out), _ptr(c_out), _ptr(violations_ptr),
+                                       F_DEVICE_PTRS | (F_SCALARS_MONT if scalars_mont else 0), channel))
 
     # ---- one process per GPU: sharded h-polynomial, distributed prove -------------------------------------------
     def h_poly_dist_dev(self, curve, comm, a_ptr, b_ptr, c_ptr, log_m, out_ptr, channel=0):
@@ -660,22 +699,26 @@ class Context:
                                                F_SCALARS_MONT if scalars_mont else 0, _ptr(out)))
         return out[:3 * nl].reshape(1, -1), out[3 * nl:9 * nl].reshape(1, -1), out[9 * nl:].reshape(1, -1)
 
-    def prove(self, pk, a, b, c, full_assignment, r, s, scalars_mont=True):
-        """Host arrays in, (A, B, C) Jacobian arrays out."""
+    def prove(self, pk, a, b, c, full_assignment, r, s, scalars_mont=True, reduction="circom"):
+        """Host arrays in, (A, B, C) Jacobian arrays out.  reduction="libsnark": pk is a LibsnarkReduction key and c = C w
+        (qap_r1cs); the default is the circom witness map."""
         a, b, c, w = (np.ascontiguousarray(v, dtype=np.uint64) for v in (a, b, c, full_assignment))
         rs = np.ascontiguousarray(np.concatenate([np.asarray(r, dtype=np.uint64).reshape(1, 4),
                                                   np.asarray(s, dtype=np.uint64).reshape(1, 4)]))
         nl = FQ_LIMBS64[pk.curve]
         out = np.zeros(3 * nl + 6 * nl + 3 * nl, dtype=np.uint64)
         self._chk(self.L.dg16_groth16_prove(self.h, pk.h, _ptr(a), _ptr(b), _ptr(c), _ptr(w), _ptr(rs),
-                                            F_SCALARS_MONT if scalars_mont else 0, _ptr(out)))
+                                            (F_SCALARS_MONT if scalars_mont else 0) | _reduction_flag(reduction),
+                                            _ptr(out)))
         return out[:3 * nl].reshape(1, -1), out[3 * nl:9 * nl].reshape(1, -1), out[9 * nl:].reshape(1, -1)
 
-    def prove_dev(self, pk, a_ptr, b_ptr, c_ptr, w_ptr, rs_host, out_ptr, scalars_mont=True, overlap_tail=False):
+    def prove_dev(self, pk, a_ptr, b_ptr, c_ptr, w_ptr, rs_host, out_ptr, scalars_mont=True, overlap_tail=False,
+                  reduction="circom"):
         """overlap_tail (DG16_F_OVERLAP_TAIL): the proof is complete on channel 2's stream (sync(2)), and the work
         enqueued next on channel 0 -- the next proof of a queue -- starts under this one's last bucket reduction."""
         rs_host = np.ascontiguousarray(rs_host, dtype=np.uint64)
-        flags = F_DEVICE_PTRS | (F_SCALARS_MONT if scalars_mont else 0) | (F_OVERLAP_TAIL if overlap_tail else 0)
+        flags = (F_DEVICE_PTRS | (F_SCALARS_MONT if scalars_mont else 0) | (F_OVERLAP_TAIL if overlap_tail else 0) |
+                 _reduction_flag(reduction))
         self._chk(self.L.dg16_groth16_prove(self.h, pk.h, _ptr(a_ptr), _ptr(b_ptr), _ptr(c_ptr), _ptr(w_ptr),
                                             _ptr(rs_host), flags, _ptr(out_ptr)))
 
@@ -692,9 +735,9 @@ class Context:
         self._chk(self.L.dg16_ntt(self.h, CURVES[curve], _ptr(data_ptr), log_n, int(inverse), _ptr(coset),
                                   F_DEVICE_PTRS, channel))
 
-    def h_poly_dev(self, curve, a_ptr, b_ptr, c_ptr, log_m, out_ptr, channel=0):
+    def h_poly_dev(self, curve, a_ptr, b_ptr, c_ptr, log_m, out_ptr, channel=0, reduction="circom"):
         self._chk(self.L.dg16_h_poly(self.h, CURVES[curve], _ptr(a_ptr), _ptr(b_ptr), _ptr(c_ptr), log_m,
-                                     _ptr(out_ptr), F_DEVICE_PTRS, channel))
+                                     _ptr(out_ptr), F_DEVICE_PTRS | _reduction_flag(reduction), channel))
 
     def gen_bases_dev(self, curve, group, seed, n, out_ptr, channel=0):
         self._chk(self.L.dg16_gen_bases(self.h, CURVES[curve], group, seed, n, _ptr(out_ptr), F_DEVICE_PTRS,

@@ -63,3 +63,28 @@ class R1CS:
         ints = [int.from_bytes(coeff[i].tobytes(), "little") for i in range(coeff.shape[0])]
         return [[(ints[j], int(col[j])) for j in range(row_ptr[i], row_ptr[i + 1])]
                 for i in range(self.n_constraints)]
+
+
+def check_witness(ctx, curve, r1cs, assignment):
+    """Is `assignment` (the full assignment [1, public.., witness..] as integers, or a uint64 [n][4] array of canonical
+    values) a satisfying one?  Runs dg16_qap_r1cs on the GPU -- the evaluation pass a Libsnark proof starts with, whose
+    fused check compares a_i b_i with c_i on every constraint row -- and returns (n_violated, first_row | None).
+    r1cs: an R1CS (canonical coefficients) or a dict with num_constraints, num_inputs, a / b / c = (row_ptr, col,
+    coeff) and coeff_mont (default True: coefficients already in Montgomery form)."""
+    if isinstance(r1cs, dict):
+        nc, ni = int(r1cs["num_constraints"]), int(r1cs["num_inputs"])
+        csr = [r1cs["a"], r1cs["b"], r1cs["c"]]
+        coeff_mont = bool(r1cs.get("coeff_mont", True))
+    else:
+        nc, ni, csr, coeff_mont = int(r1cs.n_constraints), int(r1cs.num_inputs), list(r1cs.csr), False
+    if isinstance(assignment, np.ndarray):
+        w = np.ascontiguousarray(assignment, dtype=np.uint64).reshape(-1, 4)
+    else:
+        w = np.array([[(int(x) >> (64 * j)) & (2**64 - 1) for j in range(4)] for x in assignment], dtype=np.uint64)
+    mats = []
+    for ptr, col, coeff in csr:
+        coeff = np.ascontiguousarray(coeff, dtype=np.uint64).reshape(-1, 4)
+        if not coeff_mont and coeff.shape[0]:
+            coeff = ctx.field_op(curve, "fr", "to_mont", coeff)
+        mats.append((np.ascontiguousarray(ptr, dtype=np.uint32), np.ascontiguousarray(col, dtype=np.uint32), coeff))
+    return ctx.qap_r1cs(curve, nc, ni, mats[0], mats[1], mats[2], w, scalars_mont=False)[3]

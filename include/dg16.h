@@ -87,7 +87,7 @@ enum dg16_flags {
                                ordered behind ALL of the proof (every reduction, the assembly, the copy to proof_out).  The
                                next proof with this flag fences each workspace buffer at its first reuse.  DG16_QUEUE_JOIN=1 in the environment restores the join of
                                channel 0 with the other streams at the end of the call (dg16_groth16_prove_dist keeps it). */
-  DG16_F_BASES_IN_SUBGROUP = 64u /* dg16_msm, dg16_d_msm, dg16_prove_a / _b / _c: the caller guarantees that every base is
+  DG16_F_BASES_IN_SUBGROUP = 64u, /* dg16_msm, dg16_d_msm, dg16_prove_a / _b / _c: the caller guarantees that every base is
                                in the order-r subgroup (true of any arkworks G1Affine / G2Affine obtained through
                                Validate::Yes or from CRS generation).  The library may then split the scalars with the
                                curve's endomorphism (GLV: phi(P) = lambda P holds only in that subgroup), which is what
@@ -95,6 +95,10 @@ enum dg16_flags {
                                (BN254 G1) take that path and every other group runs plain Pippenger, which -- like
                                VariableBaseMSM::msm -- is correct for ANY point of the curve.  Resident keys / tables
                                (dg16_pk_create*, dg16_bases_upload) never split and ignore the flag. */
+  DG16_F_QAP_LIBSNARK = 128u /* dg16_h_poly, dg16_groth16_setup, dg16_groth16_prove: the Libsnark QAP reduction instead of the
+                               circom one (see "The two QAP reductions" below).  Without the flag every call is unchanged.
+                               The sharded entry points (dg16_groth16_msms, dg16_groth16_msms_h, dg16_groth16_prove_dist,
+                               dg16_h_poly_dist, dg16_h_poly_dist_stage) return DG16_ERR_UNSUPPORTED with it. */
 };
 
 /* field ids for dg16_field_op: curve for the base field Fq, 16 + curve for the scalar field Fr */
@@ -127,7 +131,8 @@ int dg16_ntt(dg16_ctx *ctx, int curve, void *data, unsigned log_n, int inverse,
              const void *coset_offset, unsigned flags, int channel);
 
 /* h = NTT(shift(iNTT a)) * NTT(shift(iNTT b)) - NTT(shift(iNTT c)) on the size-2^log_m domain,
- * shift = multiply coefficient i by w_{2m}^i.  a, b, c are not modified; out may alias a. */
+ * shift = multiply coefficient i by w_{2m}^i.  a, b, c are not modified; out may alias a.
+ * With DG16_F_QAP_LIBSNARK: the coefficients of (A B - C) / Z instead ("The two QAP reductions" below). */
 int dg16_h_poly(dg16_ctx *ctx, int curve, const void *a, const void *b, const void *c,
                 unsigned log_m, void *out, unsigned flags, int channel);
 
@@ -150,6 +155,36 @@ int dg16_qap_rows(dg16_ctx *ctx, int curve, size_t num_constraints, size_t num_i
                   const uint32_t *b_row_ptr, const uint32_t *b_col, const void *b_coeff,
                   const void *full_assignment, size_t row_start, size_t row_stride, void *a_out, void *b_out,
                   void *c_out, unsigned flags, int channel);
+
+/* ---- The two QAP reductions ------------------------------------------------------------------------
+ * The reference's own words (ark-circom/src/circom/qap.rs:11-15): the circom / snarkjs witness map differs from the
+ * default LibsnarkReduction of ark-groth16 -- it takes c = a o b and evaluates on the odd coset of the doubled domain --
+ * so a key and a prover must agree on the reduction.  `Groth16::<E>` defaults to LibsnarkReduction (the reference uses
+ * it at ark-circom/src/zkey.rs:921); every arkworks circuit that is not a circom circuit, and any libsnark- or
+ * bellman-shaped key, is of that kind.  DG16_F_QAP_LIBSNARK selects it:
+ *   a, b, c   the evaluation vectors of dg16_qap, except that c[i] = <C_i, w> on the constraint rows (dg16_qap_r1cs)
+ *   h         the unique polynomial of degree <= m - 2 with h Z = A B - C, Z = X^m - 1, A, B, C the interpolants of
+ *             a, b, c on the size-m domain: dg16_h_poly returns its m coefficients (the top one zero), Montgomery form.
+ *             (Computed on the coset g H, g = F::GENERATOR; any coset off the domain gives the same h.  For a witness
+ *             that does not satisfy the R1CS the division is not exact and h is whatever the pipeline returns: ask
+ *             dg16_qap_r1cs for the violations first.)
+ *   key       h_query[i] = (tau^i Z(tau) / delta) G1 for i < m - 1, the identity at i = m - 1 (h_query keeps its 2^log_m
+ *             length: dg16_pk_create and the key layout are the same); every other element of the key is the same in
+ *             both reductions (LibsnarkReduction::instance_map_with_evaluation serves both).
+ *   proof     prove.rs:21-136 unchanged.  dg16_groth16_prove supports the flag with and without DG16_F_OVERLAP_TAIL (the
+ *             quotient's workspace is the circom h-polynomial's, touched on channel 0's stream only).
+ *
+ * dg16_qap_r1cs: dg16_qap_rows with a third CSR triple -- a = A w, b = B w, c = C w, same layout, padding, row_start /
+ * row_stride form and flags.  violations: NULL, or (device pointer iff DG16_F_DEVICE_PTRS) two uint64_t the same pass
+ * writes: [0] the number of constraint rows among those this call evaluates with a_i b_i != c_i, [1] the smallest such
+ * row index (the row of the constraint system, not the output slot), UINT64_MAX if none.  Instance and padding rows never
+ * count.  Stream-ordered on `channel` like dg16_qap; violations is valid after dg16_sync. */
+int dg16_qap_r1cs(dg16_ctx *ctx, int curve, size_t num_constraints, size_t num_inputs, size_t num_vars,
+                  unsigned log_m, const uint32_t *a_row_ptr, const uint32_t *a_col, const void *a_coeff,
+                  const uint32_t *b_row_ptr, const uint32_t *b_col, const void *b_coeff,
+                  const uint32_t *c_row_ptr, const uint32_t *c_col, const void *c_coeff,
+                  const void *full_assignment, size_t row_start, size_t row_stride, void *a_out, void *b_out,
+                  void *c_out, uint64_t *violations, unsigned flags, int channel);
 
 /* ---- MSM ----------------------------------------------------------------------------------------
  * out = sum_i scalars[i] * bases[i] in G1 (group = 1) or G2 (group = 2).
@@ -207,7 +242,9 @@ unsigned dg16_fixed_base_window_bits(size_t n);
  *   l_query [num_vars - num_inputs] G1 | fixed_points = alpha_g1 | beta_g1 | delta_g1 | beta_g2 | delta_g2 (the
  *   dg16_pk_create layout) | gamma_g2 (one G2) | gamma_abc_g1 [num_inputs] G1.
  * Synchronous in both forms (it owns temporary device memory); runs on channel 0.  A matrix entry whose column is
- * not a wire, or a row_ptr that is not ordered, is DG16_ERR_BAD_ARG. */
+ * not a wire, or a row_ptr that is not ordered, is DG16_ERR_BAD_ARG.
+ * flags | DG16_F_QAP_LIBSNARK: the LibsnarkReduction key -- h_query[i] = (tau^i Z(tau) / delta) G1 for i < m - 1 and zero
+ * bytes at i = m - 1; every other output is byte-equal to the call without the flag. */
 int dg16_groth16_setup(dg16_ctx *ctx, int curve, size_t num_constraints, size_t num_inputs, size_t num_vars,
                        unsigned log_m, const uint32_t *a_row_ptr, const uint32_t *a_col, const void *a_coeff,
                        const uint32_t *b_row_ptr, const uint32_t *b_col, const void *b_coeff,
@@ -266,7 +303,8 @@ int dg16_pk_create_shard(dg16_ctx *ctx, int curve, size_t num_vars, size_t num_i
 /* a, b, c: QAP evaluation vectors (domain_size Montgomery Fr elements each); full_assignment:
  * num_vars Fr elements [1, public.., witness..] (Montgomery iff DG16_F_SCALARS_MONT); r_s: HOST
  * pointer to r || s (2 x 32 bytes, same form as the assignment).  proof_out: A (G1 Jacobian) |
- * B (G2 Jacobian) | C (G1 Jacobian).  Uses all three channels. */
+ * B (G2 Jacobian) | C (G1 Jacobian).  Uses all three channels.  flags | DG16_F_QAP_LIBSNARK: for a LibsnarkReduction
+ * key -- h is the quotient (A B - C) / Z of the a, b, c given (c from dg16_qap_r1cs); everything after h is the same. */
 int dg16_groth16_prove(dg16_ctx *ctx, const dg16_pk *pk, const void *a, const void *b, const void *c,
                        const void *full_assignment, const void *r_s, unsigned flags, void *proof_out);
 
