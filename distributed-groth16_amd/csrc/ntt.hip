@@ -88,6 +88,8 @@ __device__ __forceinline__ unsigned bitrev(unsigned v, unsigned bits) {
 //     kFirstOut + (kMaxStepLog - 2) / 2 * kStepGrowth + kOddGrowth <= kNttBound;
 //   * the products and subtraction constants inside a step are sized for inputs up to kNttBound (their static type),
 //     which the induction above guarantees.
+// (tests/host_arith/host_arith.cpp instantiates canon() / is_zero() at this bound on the host as kCanonBound, checked by
+// tests/test_host_arith.py: change one, change the other.)
 constexpr int kNttBound = 48 * 64;
 constexpr int kNttIn = 128;               // fresh loads: canonical data, or a product with a coset / shift table (< 2 p)
 constexpr int kNttFirstOut = 9 * 64;      // first radix-4 step (three trivial twiddles): sums of four fresh loads

@@ -126,12 +126,14 @@ int dg16_field_op(dg16_ctx *ctx, int field_id, int op, const void *a, const void
  * In-place Radix2EvaluationDomain transform of 2^log_n Montgomery-form Fr elements, natural order
  * in and out.  inverse != 0 scales by n^-1.  coset_offset: NULL, or a HOST pointer to the domain
  * offset g (Montgomery form): forward multiplies coefficient i by g^i first, inverse multiplies
- * output i by g^-i. */
+ * output i by g^-i.  Every element (and g) must be reduced, i.e. below r; a non-reduced element
+ * gives an undefined result (the kernel's lazy-reduction bounds start from it). */
 int dg16_ntt(dg16_ctx *ctx, int curve, void *data, unsigned log_n, int inverse,
              const void *coset_offset, unsigned flags, int channel);
 
 /* h = NTT(shift(iNTT a)) * NTT(shift(iNTT b)) - NTT(shift(iNTT c)) on the size-2^log_m domain,
  * shift = multiply coefficient i by w_{2m}^i.  a, b, c are not modified; out may alias a.
+ * Every element of a, b, c must be reduced (below r); a non-reduced element gives an undefined result.
  * With DG16_F_QAP_LIBSNARK: the coefficients of (A B - C) / Z instead ("The two QAP reductions" below). */
 int dg16_h_poly(dg16_ctx *ctx, int curve, const void *a, const void *b, const void *c,
                 unsigned log_m, void *out, unsigned flags, int channel);

@@ -301,3 +301,36 @@ extern "C" int ha_glv_split4(int curve, const uint32_t* k, uint32_t* h0, uint32_
   }
   return 0;
 }
+
+// ---- canon() / is_zero() (and the reduce() inside canon) at the NTT tile's bound ------------------------------------------
+// kCanonBound is kNttBound of csrc/ntt.hip (a .hip file cannot be included here): every store of ntt_step_kernel ends in
+// canon() of an Fe<P, kNttBound, 1>.  Change one, change the other -- the comment at kNttBound points back here.
+constexpr int kCanonBound = 48 * 64;
+// in: n x N raw limbs of a value below 48 p -- normalised for lu = 1, lower limbs below lu 2^W for lu = 4 (norm()'s carry
+// into the top limb); words: n x NL packed words of canon(); zero: n bytes of is_zero()
+template <class P, int LU> static void canon29(const uint32_t* in, uint32_t* words, uint8_t* zero, size_t n) {
+  using T = RR<P>;
+  for (size_t i = 0; i < n; i++) {
+    Fe<P, kCanonBound, LU> v;
+    for (int j = 0; j < T::N; j++) v.l[j] = in[i * T::N + j];
+    fe_to_words<P>(canon(v), words + i * T::NL);
+    zero[i] = is_zero(v) ? 1 : 0;
+  }
+}
+template <class P> static int canon29_lu(int lu, const uint32_t* in, uint32_t* words, uint8_t* zero, size_t n) {
+  if (lu == 1) canon29<P, 1>(in, words, zero, n);
+  else if (lu == 4) canon29<P, 4>(in, words, zero, n);
+  else return 1;
+  return 0;
+}
+extern "C" int ha_canon29(int fid, int lu, const uint32_t* limbs_in, uint32_t* words_out, uint8_t* zero_out, size_t n) {
+  switch (fid) {
+    case 0: return canon29_lu<bn254_fq_params>(lu, limbs_in, words_out, zero_out, n);
+    case 1: return canon29_lu<bls12_381_fq_params>(lu, limbs_in, words_out, zero_out, n);
+    case 2: return canon29_lu<bls12_377_fq_params>(lu, limbs_in, words_out, zero_out, n);
+    case 16: return canon29_lu<bn254_fr_params>(lu, limbs_in, words_out, zero_out, n);
+    case 17: return canon29_lu<bls12_381_fr_params>(lu, limbs_in, words_out, zero_out, n);
+    case 18: return canon29_lu<bls12_377_fr_params>(lu, limbs_in, words_out, zero_out, n);
+    default: return 1;
+  }
+}

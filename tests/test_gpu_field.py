@@ -31,6 +31,65 @@ def test_field_ops_bit_exact(curve, kind):
     assert np.array_equal(c.field_op(curve, kind, "inv", A[:256]), corc.field_op(curve, kind, "inv", A[:256]))
 
 
+def boundary_values(F):
+    """Operands at the edges of the 32-bit Montgomery code of fp.h (raw limb values below p; not sampled)."""
+    p = F.p
+    nl = 2 * F.limbs64                                   # 32-bit limbs
+    top_shift = 32 * (nl - 1)
+    ptop = p >> top_shift
+    assert ptop > 1
+    vals = [0, 1, 2, p - 1, p - 2, (p - 1) // 2, (p + 1) // 2, F.R, F.R * F.R % p]
+    for k in range(32, p.bit_length(), 32):              # every 32-bit limb boundary below bits(p)
+        vals += [1 << k, (1 << k) - 1]
+    low_ones = (1 << top_shift) - 1                      # all limbs 0xFFFFFFFF below the top limb
+    vals += [(t << top_shift) | low_ones for t in (1, ptop // 2, ptop - 1)]
+    assert all(0 <= v < p for v in vals)
+    return list(dict.fromkeys(vals))
+
+
+def boundary_pairs(F):
+    p = F.p
+    S = boundary_values(F)
+    pairs = [(x, y) for x in S for y in S]
+    pairs += [(x, p - x) for x in S if x]                # the sum is exactly p
+    pairs += [(x, p - 1 - x) for x in S]                 # the sum is p - 1
+    pairs += [(x, x) for x in S]                         # subtraction: no borrow, result 0
+    pairs += [(x, x + 1) for x in S if x + 1 < p]        # subtraction: borrow through every limb, result p - 1
+    pairs += [(x, F.inv(x)) for x in S if x]
+    return pairs
+
+
+@pytest.mark.parametrize("curve", ALL)
+@pytest.mark.parametrize("kind", ["fq", "fr"])
+def test_field_ops_on_boundary_operands(curve, kind):
+    """add, sub, mul, sqr, neg, to_mont, from_mont, inv on a table of boundary operand pairs, against Python integers
+    (Montgomery R = 2^(64 limbs64): mul is a b / R, to_mont a R, from_mont a / R, inv R^2 / a on the raw values) and
+    against the C oracle.  The device product is inline assembly that exists only on the GPU."""
+    F = (FQ if kind == "fq" else FR)[curve]
+    p, R, nl = F.p, F.R, F.limbs64
+    rinv = F.inv(R)
+    pairs = boundary_pairs(F)
+    assert len(pairs) > 300
+    xs, ys = [a for a, _ in pairs], [b for _, b in pairs]
+    A, B = corc.ints_to_arr(xs, nl), corc.ints_to_arr(ys, nl)
+    want = {
+        "add": [(a + b) % p for a, b in pairs],
+        "sub": [(a - b) % p for a, b in pairs],
+        "mul": [a * b * rinv % p for a, b in pairs],
+        "sqr": [a * a * rinv % p for a in xs],
+        "neg": [(p - a) % p for a in xs],
+        "to_mont": [a * R % p for a in xs],
+        "from_mont": [a * rinv % p for a in xs],
+        "inv": [F.inv(a) * R * R % p for a in xs],
+    }
+    c = ctx()
+    for op, exp in want.items():
+        got = c.field_op(curve, kind, op, A, B)
+        bad = [i for i, (g, e) in enumerate(zip(corc.arr_to_ints(got), exp)) if g != e]
+        assert not bad, (op, len(bad), [(hex(xs[i]), hex(ys[i])) for i in bad[:4]])
+        assert np.array_equal(got, corc.field_op(curve, kind, op, A, B)), op
+
+
 def test_field_mul_million_pairs_bn254():
     # SURVEY.md section 7 step 3: >= 10^6 random pairs, bit-exact
     n = 1 << 20

@@ -33,6 +33,8 @@ def ha():
     L.ha_codec.argtypes = [i, i, i, i, vp, vp, sz, vp]
     L.ha_glv_split.argtypes = [i, vp, vp, vp, sz]
     L.ha_glv_split4.argtypes = [i, vp, vp, vp, vp, vp, sz]
+    L.ha_canon29.argtypes = [i, i, vp, vp, vp, sz]
+    L.ha_rr_consts.argtypes = [i, vp, sz]
     return L
 
 
@@ -138,6 +140,63 @@ def test_reduced_radix_field_ops(ha, curve, kind):
     assert ha.ha_field_op29(corc.fid(curve, kind), 9, _p(A), _p(B), _p(out), n) == 0
     exp = f("sub", f("mul", f("add", A, B), f("sub", A, B)), f("mul", f("add", f("add", B, B), A), A))
     assert np.array_equal(out, exp)
+
+
+def canon_boundary_values(p, W, N, rng):
+    """Values below 48 p where reduce()'s one-shot quotient estimate (top limb / (PTOP + 1)) and canon()'s single
+    conditional subtraction sit on their boundaries."""
+    top_shift = W * (N - 1)
+    ptop = p >> top_shift
+    low_ones = (1 << top_shift) - 1
+    vals = []
+    for k in range(48):
+        vals += [k * p + d for d in (0, 1, 2, p - 2, p - 1, p // 2, low_ones)]
+        if k:
+            vals.append(k * p - 1)
+        for top in (k * (ptop + 1) - 1, k * (ptop + 1), k * (ptop + 1) + 1, k * ptop, k * ptop + 1):
+            vals += [top << top_shift, (top << top_shift) | low_ones]
+    vals = [v for v in vals if 0 <= v < 48 * p]
+    return vals + [rng.randrange(48 * p) for _ in range(20000)]
+
+
+def loose_limbs(v, W, N, pick):
+    """v as N limbs whose lower limbs reach up to 4 2^W - 1: limb i borrows pick(i, available) <= 3 units of 2^W from
+    limb i + 1, so the top limb ends reduced to match and norm() has to carry all the way into it."""
+    l = [(v >> (W * i)) & ((1 << W) - 1) for i in range(N - 1)] + [v >> (W * (N - 1))]
+    for i in range(N - 1):
+        t = pick(i, min(3, l[i + 1]))
+        l[i] += t << W
+        l[i + 1] -= t
+    assert sum(x << (W * i) for i, x in enumerate(l)) == v and all(0 <= x < (4 << W) for x in l[:-1]) and l[-1] >= 0
+    return l
+
+
+@pytest.mark.parametrize("curve", ["bn254", "bls12_381", "bls12_377"])
+@pytest.mark.parametrize("kind", ["fq", "fr"])
+def test_canon_and_is_zero_at_the_ntt_bound(ha, curve, kind):
+    """fp29.h canon() (with reduce() inside) and is_zero() on Fe<P, 48 * 64, LU> -- the bound of the NTT tile (kNttBound,
+    csrc/ntt.hip), where every store of the kernel ends in canon() -- against v % p on Python integers: normalised limbs
+    (LU = 1), and the same values with lower limbs up to 4 2^W - 1 (LU = 4: norm()'s carry into the top limb), once
+    with every limb borrowing as much as it can and once with random borrows."""
+    F = (FQ if kind == "fq" else FR)[curve]
+    p, nl32, fid = F.p, 2 * F.limbs64, corc.fid(curve, kind)
+    buf = np.zeros(256, dtype=np.uint32)
+    assert ha.ha_rr_consts(fid, _p(buf), 256) > 0
+    W, N = int(buf[0]), int(buf[1])
+    rng = random.Random(48)
+    vals = canon_boundary_values(p, W, N, rng)
+    assert len(vals) > 20700 and max(vals) < 48 * p
+    exp_words = np.frombuffer(b"".join((v % p).to_bytes(4 * nl32, "little") for v in vals), dtype=np.uint32).reshape(-1, nl32)
+    exp_zero = np.array([v % p == 0 for v in vals], dtype=np.uint8)
+    assert exp_zero.sum() >= 48                                # every k p, k < 48
+    forms = [(1, lambda i, avail: 0), (4, lambda i, avail: 0), (4, lambda i, avail: avail), (4, lambda i, avail: rng.randint(0, avail))]
+    for lu, pick in forms:
+        limbs = np.array([loose_limbs(v, W, N, pick) for v in vals], dtype=np.uint32)
+        words = np.zeros((len(vals), nl32), dtype=np.uint32)
+        zero = np.full(len(vals), 7, dtype=np.uint8)
+        assert ha.ha_canon29(fid, lu, _p(limbs), _p(words), _p(zero), len(vals)) == 0
+        bad = np.flatnonzero((words != exp_words).any(axis=1) | (zero != exp_zero))
+        assert bad.size == 0, (lu, bad.size, [hex(vals[i]) for i in bad[:4]])
 
 
 # ---- arkworks compressed points: csrc/codec_impl.h on the host against the plain-Python encoder -------------------
