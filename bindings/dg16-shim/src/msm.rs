@@ -102,6 +102,42 @@ where
     }
 }
 
+/// `out[i] = scalars[i] * points[i]` (`dg16_points_mul`): n independent products in one call, where arkworks code maps
+/// `p.mul_bigint(s)` / `p * s` over a batch.  Correct for any point of the curve; `points_in_subgroup` as in [`msm`].
+pub fn points_mul<P: Dg16Config>(
+    points: &[Affine<P>],
+    scalars: &[P::ScalarField],
+    channel: c_int,
+    points_in_subgroup: bool,
+) -> Result<Vec<Affine<P>>, Dg16Error>
+where
+    P::BaseField: FieldBytes,
+{
+    if points.len() != scalars.len() {
+        return Err(Dg16Error::LengthMismatch(points.len().min(scalars.len())));
+    }
+    let packed = pack_affine(points);
+    let mut out = vec![0u8; packed.len()];
+    let mut flags: c_uint = sys::DG16_F_SCALARS_MONT;
+    if points_in_subgroup {
+        flags |= sys::DG16_F_BASES_IN_SUBGROUP;
+    }
+    check(unsafe {
+        sys::dg16_points_mul(
+            CTX.0,
+            P::CURVE,
+            P::GROUP,
+            packed.as_ptr().cast(),
+            scalars_as_bytes(scalars).as_ptr().cast(),
+            points.len(),
+            out.as_mut_ptr().cast(),
+            flags,
+            channel,
+        )
+    })?;
+    Ok(crate::setup::unpack_affine::<P>(&out))
+}
+
 /// The call-site form: `G::msm(bases, scalars)` for `G = Projective<P>` (what `d_msm::<G, _>` is instantiated with:
 /// `E::G1`, `E::G2` of the three curves).  dist-primitives/src/dmsm/mod.rs:82 under `feature = "dg16"`.
 pub trait Dg16Group: ark_ec::CurveGroup {

@@ -15,7 +15,7 @@ use ark_relations::r1cs::ConstraintMatrices;
 use ark_std::rand::RngCore;
 
 /// x || y Montgomery limbs with the identity as zeros (the library's output layout) -> `Affine<P>`.
-fn unpack_affine<P: SWCurveConfig>(buf: &[u8]) -> Vec<Affine<P>>
+pub(crate) fn unpack_affine<P: SWCurveConfig>(buf: &[u8]) -> Vec<Affine<P>>
 where
     P::BaseField: FieldBytes,
 {

@@ -124,3 +124,50 @@ where
     })?;
     Ok(accepted == 1)
 }
+
+/// `Groth16::<E>::rerandomize_proof(vk, proof, rng)` for a batch in ONE call of `dg16_groth16_rerandomize`:
+/// `(A, B, C) -> (r1^-1 A, r1 B + r1 r2 delta_g2, C + r2 A)` with `rerandomizers[i] = (r1, r2)`, both nonzero, drawn by
+/// the caller independently and uniformly per proof (the library draws no randomness; a zero is `Err`).  The proofs are
+/// not verified here and must hold subgroup points -- true of anything [`verify_batch`] accepted; the new proof
+/// verifies for the same public inputs exactly when the old one does.
+pub fn rerandomize_proofs<E, P1, P2>(pvk: &PreparedVk, proofs: &[Proof<E>],
+                                     rerandomizers: &[(E::ScalarField, E::ScalarField)])
+                                     -> Result<Vec<Proof<E>>, Dg16Error>
+where
+    E: Pairing<G1Affine = Affine<P1>, G2Affine = Affine<P2>>,
+    P1: Dg16Config<ScalarField = E::ScalarField>,
+    P2: Dg16Config<ScalarField = E::ScalarField>,
+    P1::BaseField: FieldBytes,
+    P2::BaseField: FieldBytes,
+{
+    if rerandomizers.len() != proofs.len() {
+        return Err(Dg16Error::LengthMismatch(rerandomizers.len().min(proofs.len())));
+    }
+    let mut p = Vec::new();
+    for pr in proofs {
+        p.extend(pack_affine(&[pr.a]));
+        p.extend(pack_affine(&[pr.b]));
+        p.extend(pack_affine(&[pr.c]));
+    }
+    let mut r = Vec::with_capacity(proofs.len() * 64);
+    for (r1, r2) in rerandomizers {
+        r.extend_from_slice(scalars_as_bytes(&[*r1, *r2]));
+    }
+    let mut out = vec![0u8; p.len()];
+    check(unsafe {
+        sys::dg16_groth16_rerandomize(
+            CTX.0, pvk.h, p.as_ptr().cast(), proofs.len(), r.as_ptr().cast(), sys::DG16_F_SCALARS_MONT,
+            out.as_mut_ptr().cast(), 0,
+        )
+    })?;
+    let g1 = 2 * <P1::BaseField as FieldBytes>::BYTES;
+    let g2 = 2 * <P2::BaseField as FieldBytes>::BYTES;
+    Ok(out
+        .chunks_exact(2 * g1 + g2)
+        .map(|c| Proof {
+            a: crate::setup::unpack_affine::<P1>(&c[..g1])[0],
+            b: crate::setup::unpack_affine::<P2>(&c[g1..g1 + g2])[0],
+            c: crate::setup::unpack_affine::<P1>(&c[g1 + g2..])[0],
+        })
+        .collect())
+}

@@ -309,6 +309,14 @@ extern "C" {
                                          n_public: usize, proofs_affine: *const c_void, n_proofs: usize,
                                          coeffs: *const c_void, flags: c_uint, accepted: *mut u8, channel: c_int)
                                          -> c_int;
+    // ---- batched point multiplication and proof re-randomization ----
+    pub fn dg16_points_mul(ctx: *mut Dg16Ctx, curve: c_int, group: c_int, points_affine: *const c_void,
+                           scalars: *const c_void, n: usize, out_affine: *mut c_void, flags: c_uint, channel: c_int)
+                           -> c_int;
+    pub fn dg16_ctx_set_points_mul_slice(ctx: *mut Dg16Ctx, products: usize) -> c_int;
+    pub fn dg16_groth16_rerandomize(ctx: *mut Dg16Ctx, vk: *const Dg16Vk, proofs_affine: *const c_void,
+                                    n_proofs: usize, r1_r2: *const c_void, flags: c_uint, proofs_out: *mut c_void,
+                                    channel: c_int) -> c_int;
     // ---- dist-primitives over an MpcNet (packed secret sharing): d_fft, d_msm, d_pp, deg_red, ext_wit::h, prove::A/B/C ----
     pub fn dg16_pss_create(ctx: *mut Dg16Ctx, curve: c_int, l: c_uint, out: *mut *mut Dg16Pss) -> c_int;
     pub fn dg16_d_fft(ctx: *mut Dg16Ctx, pp: *const Dg16Pss, net: *const Dg16Net, share: *const c_void,

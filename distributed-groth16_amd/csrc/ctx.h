@@ -97,6 +97,8 @@ struct dg16_ctx {
   // HBM budget of the window tables of ONE resident key / base set built from here on (dg16_ctx_set_table_budget);
   // 0 = unlimited (one table row per window)
   size_t table_budget = 0;
+  // products per launch of dg16_points_mul (dg16_ctx_set_points_mul_slice); 0 = points_mul.h's default
+  size_t points_mul_slice = 0;
   std::map<dg16::TwiddleKey, dg16::TwiddleSet> twiddles;
   std::map<std::pair<int, unsigned>, dg16::CosetSet> cosets;   // (curve, log_m); guarded by mu like the twiddles
 };

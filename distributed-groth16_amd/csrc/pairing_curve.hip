@@ -87,6 +87,8 @@ bool vk_prepare<DG_CURVE>(const void* alpha_g1, const void* beta_g2, const void*
   VkData d;
   try {
     d.n_ic = n_ic;
+    static_assert(sizeof delta <= sizeof d.delta_point, "delta_g2 does not fit VkData::delta_point");
+    memcpy(d.delta_point, &delta, sizeof delta);
     d.ic = upload(icv.data(), n_ic * sizeof(Affine<Fq>));
     if (!gamma.is_inf()) d.gamma = upload(tg.data(), tg.size() * sizeof(P::Line));
     if (!delta.is_inf()) d.delta = upload(td.data(), td.size() * sizeof(P::Line));

@@ -15,6 +15,8 @@ struct VkData {            // a prepared verifying key: device memory owned by t
   // what the aggregate verifier pairs instead of alpha_beta (its pair is (-s_0 alpha, beta), s_0 known per call)
   void* beta = nullptr;        // the Miller-loop lines of beta_g2 (null: beta is the identity)
   void* neg_alpha = nullptr;   // -alpha_g1, one affine G1 point
+  // delta_g2 itself (affine, host memory; 192 bytes hold the larger curve's): dg16_groth16_rerandomize multiplies it
+  alignas(16) uint8_t delta_point[192] = {};
 };
 
 // Validates the key (host pointers), does the per-key work on the host and uploads it; false = malformed key.

@@ -251,6 +251,9 @@ def load():
     L.dg16_vk_destroy.restype = None
     L.dg16_groth16_verify_batch.argtypes = [vp, vp, vp, sz, vp, sz, u, vp, i]
     L.dg16_groth16_verify_aggregate.argtypes = [vp, vp, vp, sz, vp, sz, vp, u, vp, i]
+    L.dg16_points_mul.argtypes = [vp, i, i, vp, vp, sz, vp, u, i]
+    L.dg16_ctx_set_points_mul_slice.argtypes = [vp, sz]
+    L.dg16_groth16_rerandomize.argtypes = [vp, vp, vp, sz, vp, u, vp, i]
     _lib = L
     return L
 
@@ -274,7 +277,8 @@ EXPORTED = ["dg16_ctx_create", "dg16_ctx_destroy", "dg16_last_error", "dg16_set_
             "dg16_zkey_free", "dg16_serialize_error", "dg16_proof_compress", "dg16_proof_decompress",
             "dg16_verify_error", "dg16_groth16_verify", "dg16_prove_a", "dg16_prove_b", "dg16_prove_c",
             "dg16_ctx_set_table_budget", "dg16_fixed_base_mul", "dg16_fixed_base_window_bits", "dg16_groth16_setup",
-            "dg16_vk_create", "dg16_vk_destroy", "dg16_groth16_verify_batch", "dg16_groth16_verify_aggregate"]
+            "dg16_vk_create", "dg16_vk_destroy", "dg16_groth16_verify_batch", "dg16_groth16_verify_aggregate",
+            "dg16_points_mul", "dg16_ctx_set_points_mul_slice", "dg16_groth16_rerandomize"]
 
 
 def _ptr(x):
@@ -522,6 +526,38 @@ class Context:
         self._chk(self.L.dg16_fixed_base_mul(self.h, CURVES[curve], group, _ptr(base), _ptr(scalars), scalars.shape[0],
                                              _ptr(out), F_SCALARS_MONT if scalars_mont else 0, channel))
         return out
+
+    def points_mul(self, curve, group, points, scalars, scalars_mont=False, in_subgroup=False, device=False, channel=0,
+                   out=None, n=None):
+        """out[i] = scalars[i] * points[i] (`dg16_points_mul`): affine points (identity = zeros), uint64 [n][4] scalars
+        below 2^255 or in Montgomery form.  Correct for any point of the curve; in_subgroup=True (every point is in the
+        order-r subgroup) lets the library split the scalars with the curve's endomorphism.  device=True: points, scalars
+        and out are device pointers (ints) or objects with data_ptr(), n is required, the call is stream-ordered on the
+        channel, and out=None means in place (out = points).  Returns the products (host arrays) or `out` (device)."""
+        flags = (F_SCALARS_MONT if scalars_mont else 0) | (F_BASES_IN_SUBGROUP if in_subgroup else 0)
+        if device:
+            ptr = lambda x: x.data_ptr() if hasattr(x, "data_ptr") else int(x or 0)
+            if n is None:
+                raise ValueError("n is required with device pointers")
+            if out is None:
+                out = points
+            self._chk(self.L.dg16_points_mul(self.h, CURVES[curve], group, ctypes.c_void_p(ptr(points)),
+                                             ctypes.c_void_p(ptr(scalars)), n, ctypes.c_void_p(ptr(out)),
+                                             flags | F_DEVICE_PTRS, channel))
+            return out
+        nl = FQ_LIMBS64[curve] * 2 * (2 if group == 2 else 1)
+        points = np.ascontiguousarray(points, dtype=np.uint64).reshape(-1, nl)
+        scalars = np.ascontiguousarray(scalars, dtype=np.uint64).reshape(-1, 4)
+        if points.shape[0] != scalars.shape[0]:
+            raise ValueError("points and scalars differ in length")
+        res = np.zeros_like(points)
+        self._chk(self.L.dg16_points_mul(self.h, CURVES[curve], group, _ptr(points), _ptr(scalars), points.shape[0],
+                                         _ptr(res), flags, channel))
+        return res
+
+    def set_points_mul_slice(self, products):
+        """Products per launch of `points_mul` (0 = the library's default); bounds its table workspace."""
+        self._chk(self.L.dg16_ctx_set_points_mul_slice(self.h, int(products)))
 
     def fixed_base_mul_dev(self, curve, group, scalars_ptr, n, out_ptr, base=None, scalars_mont=False, channel=0):
         """Device pointers for the scalars and the output (stream-ordered on the channel); base stays a host array."""

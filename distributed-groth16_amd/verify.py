@@ -48,6 +48,22 @@ def random_coefficients(n):
     return np.frombuffer(bytes(buf), dtype=np.uint64).reshape(n, 2)
 
 
+def random_rerandomizers(curve, n):
+    """n pairs (r1, r2) for `PreparedVerifyingKey.rerandomize`, each uniform in [1, r) by rejection from the operating
+    system's generator: n x 2 x 4 uint64, canonical."""
+    from .keygen import FR_MODULUS
+    r = FR_MODULUS[curve]
+    nbits = r.bit_length()
+    out = np.zeros((n, 2, 4), dtype=np.uint64)
+    for i in range(n):
+        for j in range(2):
+            v = 0
+            while not 1 <= v < r:
+                v = secrets.randbits(nbits)
+            out[i, j] = np.frombuffer(v.to_bytes(32, "little"), dtype=np.uint64)
+    return out
+
+
 class PreparedVerifyingKey:
     """A verifying key validated and prepared once on `ctx`'s GPU (`ark_groth16::PreparedVerifyingKey`): the Miller value
     of (alpha, beta) and the Miller-loop line tables of gamma and delta.  Raises Dg16Error(BAD_ARG) for a malformed key
@@ -151,6 +167,40 @@ class PreparedVerifyingKey:
         ctx._chk(L.dg16_groth16_verify_aggregate(ctx.h, self.h, p(pub), n_public, p(proofs), n, p(coeffs), flags,
                                                  p(out), channel))
         return bool(out[0])
+
+    def rerandomize(self, proofs, r1_r2=None, scalars_mont=False, device=False, channel=0, n_proofs=None, out=None):
+        """`Groth16::rerandomize_proof` for a batch (`dg16_groth16_rerandomize`): (A, B, C) -> (r1^-1 A,
+        r1 B + r1 r2 delta_g2, C + r2 A), which verifies for the same public inputs exactly when (A, B, C) does and cannot
+        be linked to it.  proofs as in `verify_batch`; r1_r2: n_proofs x 2 scalars in [1, r) (4 uint64 each), None draws
+        them with `random_rerandomizers`.  The proofs are not verified here and must hold subgroup points: verify first.
+        Host arrays: a zero or non-reduced r1 / r2 raises Dg16Error(BAD_ARG).  device=True: proofs, r1_r2 and out are
+        device pointers, r1_r2 and n_proofs are required, out=None means in place, the call is stream-ordered on the
+        channel, and a bad r1 / r2 turns its proof into all-zero bytes instead of an error.  Returns the new proofs."""
+        flags = _lib.F_SCALARS_MONT if scalars_mont else 0
+        L, ctx = self.ctx.L, self.ctx
+        if device:
+            ptr = lambda x: x.data_ptr() if hasattr(x, "data_ptr") else int(x or 0)
+            if n_proofs is None or r1_r2 is None:
+                raise ValueError("n_proofs and r1_r2 are required with device pointers")
+            if out is None:
+                out = proofs
+            ctx._chk(L.dg16_groth16_rerandomize(ctx.h, self.h, ctypes.c_void_p(ptr(proofs)), n_proofs,
+                                                ctypes.c_void_p(ptr(r1_r2)), flags | _lib.F_DEVICE_PTRS,
+                                                ctypes.c_void_p(ptr(out)), channel))
+            return out
+        proofs = np.ascontiguousarray(proofs, dtype=np.uint64).reshape(-1, 8 * self.fq)
+        n = proofs.shape[0]
+        if r1_r2 is None:
+            if scalars_mont:
+                raise ValueError("drawn r1, r2 are canonical: pass scalars_mont=False")
+            r1_r2 = random_rerandomizers(self.curve, n)
+        r1_r2 = np.ascontiguousarray(r1_r2, dtype=np.uint64).reshape(-1, 2, 4)
+        if r1_r2.shape[0] != n:
+            raise ValueError("r1_r2 is not n_proofs x 2 scalars")
+        res = np.zeros_like(proofs)
+        p = lambda x: x.ctypes.data_as(ctypes.c_void_p)
+        ctx._chk(L.dg16_groth16_rerandomize(ctx.h, self.h, p(proofs), n, p(r1_r2), flags, p(res), channel))
+        return res
 
     def close(self):
         if self.h:

@@ -678,6 +678,38 @@ int dg16_groth16_verify_aggregate(dg16_ctx *ctx, const dg16_vk *vk, const void *
                                   const void *coeffs /* n_proofs x 16 bytes, little-endian unsigned */, unsigned flags,
                                   uint8_t *accepted /* ONE byte */, int channel);
 
+/* ---- Batched point multiplication and Groth16 proof re-randomization ------------------------------------------------
+ * out[i] = scalars[i] * points[i], i < n.  points / out: affine x || y Montgomery limbs of the group's coordinate
+ * field, identity = all-zero bytes (the layout of dg16_fixed_base_mul's output and of dg16_groth16_verify_batch's
+ * proofs).  scalars: n x 32 bytes, integers below 2^255 (canonical field elements are), or Montgomery form with
+ * DG16_F_SCALARS_MONT.  All three curves, group 1 or 2.  Correct for ANY point of the curve, like dg16_msm; the points
+ * are neither checked to be on the curve nor in the subgroup (dg16_points_decompress(validate) does that).  With
+ * DG16_F_BASES_IN_SUBGROUP the library splits the scalars with the curve's endomorphism (half or a quarter of the
+ * doublings); without it only the cofactor-one group (BN254 G1) is split: the rule of dg16_msm.  Host pointers:
+ * synchronous.  DG16_F_DEVICE_PTRS: stream-ordered on `channel`.  out may be the same buffer as points, not a partial
+ * overlap.  n = 0 is DG16_OK; a null pointer with n > 0 or a group other than 1 or 2 is DG16_ERR_BAD_ARG, an unknown
+ * curve DG16_ERR_BAD_CURVE.  Temporaries come from the channel's workspace (DG16_ERR_OOM leaves the context usable); a
+ * large n is processed in slices of 2^16 products (dg16_ctx_set_points_mul_slice changes that for contexts short of
+ * memory and for tests: 0 = default, at most 2^20; rounded up to a multiple of 64). */
+int dg16_points_mul(dg16_ctx *ctx, int curve, int group, const void *points_affine, const void *scalars, size_t n,
+                    void *out_affine, unsigned flags, int channel);
+int dg16_ctx_set_points_mul_slice(dg16_ctx *ctx, size_t products);
+/* proofs_out[i] = (A', B', C'),  A' = r1^-1 A,  B' = r1 B + (r1 r2) delta_g2,  C' = C + r2 A
+ * (ark_groth16::Groth16::rerandomize_proof; figure 1 of Baghery-Kohlweiss-Siim-Volkhov).  Key handle, proof layout
+ * (n_proofs x (A | B | C), affine), curves (BN254, BLS12-381) and flags (DG16_F_SCALARS_MONT, DG16_F_DEVICE_PTRS only)
+ * are those of dg16_groth16_verify_batch.  r1_r2: n_proofs x (r1 | r2), 2 x 32 bytes, each in [1, r).
+ * THE RANDOMNESS IS THE CALLER'S (as r, s of the prover and the aggregate verifier's coefficients): independent and
+ * uniform per proof.  The proofs are NOT verified or validated here: (A', B', C') satisfies the verification equation
+ * for the same public inputs exactly when (A, B, C) does (both sides gain the factor e(r2 A, delta)); verify first.
+ * The caller guarantees that the points are on their curves and in the order-r subgroups (true of any proof
+ * dg16_groth16_verify_batch accepted): the products use the endomorphism split.  Identity points are legal (A = 0 gives
+ * A' = 0 and C' = C).  proofs_out may be proofs_affine.  n_proofs = 0 is DG16_OK.
+ * An r1 or r2 that is zero or >= r: with host pointers DG16_ERR_BAD_ARG, checked before any work; with
+ * DG16_F_DEVICE_PTRS the kernel checks, writes an ALL-ZERO proof (three identities, which no verifier accepts for a
+ * real key) at that index, and the call returns DG16_OK. */
+int dg16_groth16_rerandomize(dg16_ctx *ctx, const dg16_vk *vk, const void *proofs_affine, size_t n_proofs,
+                             const void *r1_r2, unsigned flags, void *proofs_out, int channel);
+
 /* Duration in milliseconds of the dominant kernel(s) of the most recent call on `channel`
  * (HIP events recorded on the channel's stream); 0 if none.  which: 0 = whole call,
  * 1 = bucket accumulation (MSM) / butterfly passes (NTT); 2 = NOT a duration: the shader clock in MHz the chip held
