@@ -578,9 +578,15 @@ int dg16_ext_wit_h(dg16_ctx* ctx, const dg16_pss* pp, const dg16_net* net, const
                    const void* c_share, unsigned log_m, void* out, unsigned flags) {
   if (!ctx) return DG16_ERR_BAD_ARG;
   return guarded(ctx, [&] {
-    DG_REQUIRE(pp && net && a_share && b_share && c_share && out, DG16_ERR_BAD_ARG, "bad argument");
+    DG_REQUIRE(pp && net && a_share && b_share && c_share && out && log_m < 48, DG16_ERR_BAD_ARG, "bad argument");
+    DG_REQUIRE(net->n_parties(net->self) == pp->n, DG16_ERR_BAD_ARG, "net.n_parties() != pp.n");
     const unsigned n = pp->n, l = pp->l;
     const size_t m = (size_t)1 << log_m, mbyl = m / l;
+    DG_REQUIRE(m >= l, DG16_ERR_BAD_ARG, "domain smaller than the packing factor (m / l == 0)");
+    // `s1.swap(i, i * pp.l + pp.t)` for i < m on a vector of 2m (ext_wit.rs:74-76) indexes past its end unless l <= 2:
+    // the reference panics there.  Every party holds the same pp, so every party returns here, before any collective.
+    DG_REQUIRE((m - 1) * l + pp->t < 2 * m, DG16_ERR_UNSUPPORTED,
+               "ext_wit::h takes the odd positions of the unpacked evaluations: l <= 2 only, like the reference");
     bool dev = flags & DG16_F_DEVICE_PTRS;
     Call k(ctx, 0);
     FR_SWITCH(pp->curve, {

@@ -43,7 +43,8 @@ __device__ Fr generator_dev() {
   return g;
 }
 
-// one thread per matrix entry; layout documented at dg16_pss::mats
+// One workgroup.  The Montgomery matrices: one thread per entry (n l <= 256 for l <= 8).  Below the barrier, strided over
+// the workgroup: the 3 n l canonical copies and the n sums v2sum.  Layout documented at dg16_pss::mats.
 template <class Fr>
 __global__ void pss_setup_kernel(unsigned l, Fr* mats) {
   const unsigned n = 4 * l, s = 2 * l;
@@ -81,11 +82,12 @@ __global__ void pss_setup_kernel(unsigned l, Fr* mats) {
     }
   }
   __syncthreads();
-  if (tid < 3 * n * l) canon[tid] = mats[tid].from_mont();
-  if (tid < n) {
+  // 3 n l = 768 entries at l = 8, more than the workgroup has threads
+  for (unsigned e = tid; e < 3 * n * l; e += blockDim.x) canon[e] = mats[e].from_mont();
+  for (unsigned j = tid; j < n; j += blockDim.x) {
     Fr acc = Fr::zero();
-    for (unsigned i = 0; i < l; i++) acc = acc + unpack2[i * n + tid];
-    v2sum[tid] = acc.from_mont();
+    for (unsigned i = 0; i < l; i++) acc = acc + unpack2[i * n + j];
+    v2sum[j] = acc.from_mont();
   }
 }
 

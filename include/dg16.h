@@ -462,6 +462,8 @@ void dg16_localnet_destroy(dg16_localnet *net);
 void dg16_localnet_abort(dg16_localnet *net);
 void dg16_localnet_reset(dg16_localnet *net, unsigned timeout_s);
 
+/* l: the packing factor, 1, 2, 4 or 8 (n = 4 l = 4, 8, 16 or 32 parties, t = l - 1); anything else is
+ * DG16_ERR_BAD_ARG.  Every primitive below takes every accepted l except dg16_ext_wit_h (see there). */
 int dg16_pss_create(dg16_ctx *ctx, int curve, unsigned l, dg16_pss **out);
 void dg16_pss_destroy(dg16_pss *pp);
 /* which: 0 pack ([count][l] -> [count][n]), 1 unpack ([count][n] -> [count][l]), 2 unpack2 */
@@ -488,7 +490,14 @@ int dg16_deg_red(dg16_ctx *ctx, const dg16_pss *pp, const dg16_net *net, const v
 int dg16_d_pp(dg16_ctx *ctx, const dg16_pss *pp, const dg16_net *net, const void *num, const void *den,
               size_t count, void *out, unsigned flags, int channel);
 /* a/b/c_share: this party's PackedQAPShare vectors (m/l each); out: m/l packed shares of h.
- * Uses channel 0 (the reference multiplexes channels 0..2 for the three transforms). */
+ * Uses channel 0 (the reference multiplexes channels 0..2 for the three transforms).
+ * l <= 2 only, as in the reference: its `s1.swap(i, i * pp.l + pp.t)` for i < m on the 2m unpacked evaluations
+ * (ext_wit.rs:74-76) indexes past the vector for l = 4 or 8 and panics; here those l return DG16_ERR_UNSUPPORTED.
+ * 2^log_m < l, log_m >= 48 and net.n_parties() != pp.n are DG16_ERR_BAD_ARG.  All three are decided from pp and log_m alone, before
+ * any collective: every party gets the same code and nobody waits.
+ * At l = 2 the result is the packed sharing of CircomReduction's witness map.  At l = 1 (t = 0) the swap is the
+ * identity, so the reference keeps the FIRST m of the 2m evaluations, not the odd ones: the call mirrors that output
+ * share for share, and it is NOT the witness map. */
 int dg16_ext_wit_h(dg16_ctx *ctx, const dg16_pss *pp, const dg16_net *net, const void *a_share,
                    const void *b_share, const void *c_share, unsigned log_m, void *out, unsigned flags);
 /* prove::A::compute (groth16/src/prove.rs:21-46): out = L + N * r + d_msm(S, a) on `channel` (the reference's `sid`).

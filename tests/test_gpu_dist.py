@@ -17,20 +17,11 @@ from oracle.pyref import dist as R, groth16 as G
 
 pytestmark = pytest.mark.gpu
 
-_state = {}
-
 
 def parties(curve, l=2):
-    """n contexts + params + net, cached per (curve, l)."""
-    key = (curve, l)
-    if key not in _state:
-        import dg16_amd
-        from dg16_amd import dist as D
-        n = 4 * l
-        ctxs = [dg16_amd.Context(0) for _ in range(n)]
-        pps = [D.PackedSharingParams(c, curve, l) for c in ctxs]
-        _state[key] = (ctxs, pps, D.LocalTestNet(n), D)
-    return _state[key]
+    """n contexts + params + net per (curve, l), from the pool every distributed-primitive module shares."""
+    import dist_pool
+    return dist_pool.parties(curve, l)
 
 
 def enc(F, vals):
