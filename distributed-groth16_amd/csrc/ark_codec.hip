@@ -4,7 +4,9 @@
 //
 // Two layers:
 //   dg16_arkkey_layout      host code: walks the container -- field order of the derive macro, u64 little-endian
-//                           lengths in front of every Vec -- and returns counts and byte offsets
+//                           lengths in front of every Vec -- and returns counts and byte offsets.  It lives in
+//                           formats.hip with the other container readers (pure host code, built and fuzzed with the
+//                           host compiler: tests/host_mutation/), and so does the text dg16_codec_error returns
 //   dg16_points_compress /  the batched point codec on the GPU, one lane per point: the SAME encode / decode routines
 //   dg16_points_decompress  as the proof.bin codec (codec_impl.h, pinned by the reference's own proof.bin), so a
 //                           2^20-point query decompresses (one 254-bit exponentiation per G1 point for the square
@@ -18,6 +20,8 @@
 #include "ctx.h"
 
 namespace dg16 {
+
+std::string& codec_error_text();   // formats.hip: what dg16_codec_error returns (one per thread)
 
 template <int CURVE, class F>
 __global__ void __launch_bounds__(64) points_encode_kernel(const Affine<F>* __restrict__ in, size_t n,
@@ -101,19 +105,11 @@ __global__ void __launch_bounds__(256) wire_fr_decode_kernel(const uint32_t* __r
 using namespace dg16;
 
 namespace {
-thread_local std::string g_codec_err;
 const char* kCodecErr[5] = {"", "invalid flags", "coordinate not reduced", "x is not on the curve",
                             "point is not in the prime-order subgroup"};
-uint64_t rd64(const uint8_t* p) {
-  uint64_t v;
-  memcpy(&v, p, 8);
-  return v;
-}
 }  // namespace
 
 extern "C" {
-
-const char* dg16_codec_error(void) { return g_codec_err.c_str(); }
 
 int dg16_points_compress(dg16_ctx* ctx, int curve, int group, const void* affine, size_t n, void* out, unsigned flags,
                          int channel) {
@@ -170,8 +166,8 @@ int dg16_points_decompress(dg16_ctx* ctx, int curve, int group, const void* in, 
     DG_HIP(hipStreamSynchronize(k.s()));
     if (tag != ~0ull) {
       const unsigned code = (unsigned)(tag & 0xFF);
-      g_codec_err = std::string(kCodecErr[code < 5 ? code : 0]) + " (point " + std::to_string((tag >> 8) - 1) + ")";
-      throw StatusError{DG16_ERR_BAD_ARG, g_codec_err};
+      codec_error_text() = std::string(kCodecErr[code < 5 ? code : 0]) + " (point " + std::to_string((tag >> 8) - 1) + ")";
+      throw StatusError{DG16_ERR_BAD_ARG, codec_error_text()};
     }
   });
 }
@@ -222,8 +218,8 @@ int dg16_wire_fr_decode(dg16_ctx* ctx, int curve, const void* in, size_t bytes, 
     DG_HIP(hipMemcpyAsync(&len, din, 8, hipMemcpyDeviceToHost, k.s()));
     DG_HIP(hipStreamSynchronize(k.s()));
     if (len != (bytes - 8) / 32 || (bytes - 8) % 32) {
-      g_codec_err = "Vec<F>: length prefix does not match the payload";
-      throw StatusError{DG16_ERR_BAD_ARG, g_codec_err};
+      codec_error_text() = "Vec<F>: length prefix does not match the payload";
+      throw StatusError{DG16_ERR_BAD_ARG, codec_error_text()};
     }
     const size_t n = (size_t)len;
     *n_out = n;
@@ -247,46 +243,10 @@ int dg16_wire_fr_decode(dg16_ctx* ctx, int curve, const void* in, size_t bytes, 
     k.finish();
     DG_HIP(hipStreamSynchronize(k.s()));
     if (tag != ~0ull) {
-      g_codec_err = "Vec<F>: element " + std::to_string((tag >> 8) - 1) + " is not reduced";
-      throw StatusError{DG16_ERR_BAD_ARG, g_codec_err};
+      codec_error_text() = "Vec<F>: element " + std::to_string((tag >> 8) - 1) + " is not reduced";
+      throw StatusError{DG16_ERR_BAD_ARG, codec_error_text()};
     }
   });
-}
-
-int dg16_arkkey_layout(const void* data, size_t bytes, int verifying_key_only, dg16_arkkey_layout_t* out) {
-  if (!data || !out) return DG16_ERR_BAD_ARG;
-  memset(out, 0, sizeof(*out));
-  const uint8_t* p = (const uint8_t*)data;
-  size_t at = 0;
-  auto need = [&](size_t k) {
-    if (at + k > bytes || at + k < at) { g_codec_err = "key file truncated"; return false; }
-    return true;
-  };
-  auto fixed = [&](uint64_t& off, size_t k) {
-    if (!need(k)) return false;
-    off = at;
-    at += k;
-    return true;
-  };
-  auto vec = [&](uint64_t& off, uint64_t& count, size_t each) {
-    if (!need(8)) return false;
-    count = rd64(p + at);
-    at += 8;
-    if (count > (bytes - at) / each) { g_codec_err = "key file truncated (vector length exceeds the file)"; return false; }
-    off = at;
-    at += (size_t)count * each;
-    return true;
-  };
-  bool ok = fixed(out->off_alpha_g1, 32) && fixed(out->off_beta_g2, 64) && fixed(out->off_gamma_g2, 64) &&
-            fixed(out->off_delta_g2, 64) && vec(out->off_ic, out->n_ic, 32);
-  if (ok && !verifying_key_only)
-    ok = fixed(out->off_beta_g1, 32) && fixed(out->off_delta_g1, 32) && vec(out->off_a, out->n_a, 32) &&
-         vec(out->off_b1, out->n_b1, 32) && vec(out->off_b2, out->n_b2, 64) && vec(out->off_h, out->n_h, 32) &&
-         vec(out->off_l, out->n_l, 32);
-  if (!ok) return DG16_ERR_BAD_ARG;
-  if (at != bytes) { g_codec_err = "trailing bytes after the key"; return DG16_ERR_BAD_ARG; }
-  out->bytes = at;
-  return DG16_OK;
 }
 
 }  // extern "C"

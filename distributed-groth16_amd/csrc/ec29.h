@@ -59,6 +59,19 @@ template <class P> struct FieldOf<Fp2<Fp<P>>> {
   DG_HD static Store from32(const Fp2<Fp<P>>& a) { return {fit<BS>(fe_from_fp(a.c0)), fit<BS>(fe_from_fp(a.c1))}; }
 };
 
+// A curve y^2 = x^3 + b has a point with y = 0 -- a point of order two -- iff -b is a cube in the coordinate field, iff
+// the order of the curve group is even.  Of the six groups here only BLS12-377 G1 has one: T = (q - 1, 0) (b = 1, even
+// cofactor; tests/test_codec_cases.py checks all six).  Doubling T must give the identity, and the identity is told by
+// zz with ALL LIMBS zero: the formulas below give zz = (2 y)^2 = 0 mod p, but with y = k p (the negative of a canonical
+// zero: neg() is K p - y) the Montgomery product of two multiples of p is a multiple of p, not the zero limbs.  So every
+// doubling of a field that can meet y = 0 tests it and returns the identity itself; the other fields compile as before.
+template <class F> struct HasOrderTwoPoint { static constexpr bool value = false; };
+template <> struct HasOrderTwoPoint<Fp<bls12_377_fq_params>> { static constexpr bool value = true; };
+// u = 0 (mod p) for a u that may EQUAL its static bound: neg(0) is K p, exactly (Bound / 64) p -- one candidate more than
+// is_zero (values BELOW the bound) tries
+template <class P, int B, int LU>
+DG_HD bool is_zero_up_to_bound(const Fe<P, B, LU>& u) { return is_zero(norm(u).template as<B + 64, 1>()); }
+
 // affine point in internal form, canonical coordinates; identity = (0, 0)
 template <class F>
 struct Affine29 {
@@ -84,6 +97,9 @@ struct XYZZ29 {
   template <class FX, class FY>
   DG_HD static XYZZ29 dbl_affine(const FX& qx, const FY& qy) {
     const auto u = dbl(qy);
+    if constexpr (HasOrderTwoPoint<F>::value) {
+      if (is_zero_up_to_bound(u)) return inf();
+    }
     const auto v = sqr(u);
     const auto w = u * v;
     const auto s = qx * v;
@@ -97,6 +113,9 @@ struct XYZZ29 {
   DG_HD XYZZ29 dbl_pt() const {
     if (is_inf()) return *this;
     const auto u = dbl(y);
+    if constexpr (HasOrderTwoPoint<F>::value) {
+      if (is_zero_up_to_bound(u)) return inf();
+    }
     const auto v = sqr(u);
     const auto w = u * v;
     const auto s = x * v;
@@ -297,6 +316,12 @@ struct XYZZ29 {
       return;
     }
     const auto u = dbl(a->y);
+    if constexpr (HasOrderTwoPoint<F>::value) {
+      if (is_zero_up_to_bound(u)) {
+        *dst = inf();
+        return;
+      }
+    }
     const auto v = sqr(u);
     const auto w = u * v;
     DG29_STAGE();

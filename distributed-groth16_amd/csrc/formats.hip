@@ -1,4 +1,4 @@
-// circom `.r1cs` and snarkjs `.zkey` readers -- host side of libdg16 (no GPU work here), the native counterpart of
+// circom `.r1cs` and snarkjs `.zkey` readers and the container walk of arkworks key files -- host side of libdg16 (no GPU work here), the native counterpart of
 // the reference's Rust readers: ark-circom/src/circom/r1cs_reader.rs:54-249 (R1CSFile::new) and
 // ark-circom/src/zkey.rs:53-388 (read_zkey).  Same acceptance rules and error texts as the reference; the zkey
 // reader is zero-copy: points in a zkey are x || y Montgomery limbs with the identity as (0, 0), which is
@@ -9,6 +9,7 @@
 #include <map>
 #include <memory>
 #include <new>
+#include <stdexcept>
 #include <string>
 #include <vector>
 
@@ -316,5 +317,58 @@ int dg16_zkey_matrix(const dg16_zkey* z, int which, dg16_csr* out) {
 }
 
 void dg16_zkey_free(dg16_zkey* z) { delete z; }
+
+}  // extern "C"
+
+// ---- arkworks compressed key files: the container (the points themselves are decoded on the GPU, ark_codec.hip) -------
+// Pure host code like the two readers above, so that the whole layer that walks untrusted containers builds with the
+// host compiler alone (tests/host_mutation/).  The error text is the codec's: dg16_codec_error returns what this walk
+// or the batched point codec said last on the calling thread.
+namespace dg16 {
+std::string& codec_error_text() {
+  thread_local std::string text;
+  return text;
+}
+}  // namespace dg16
+
+extern "C" {
+
+const char* dg16_codec_error(void) { return dg16::codec_error_text().c_str(); }
+
+int dg16_arkkey_layout(const void* data, size_t bytes, int verifying_key_only, dg16_arkkey_layout_t* out) {
+  if (!data || !out) return DG16_ERR_BAD_ARG;
+  memset(out, 0, sizeof(*out));
+  const uint8_t* p = (const uint8_t*)data;
+  size_t at = 0;
+  auto need = [&](size_t k) {
+    if (at + k > bytes || at + k < at) { dg16::codec_error_text() = "key file truncated"; return false; }
+    return true;
+  };
+  auto fixed = [&](uint64_t& off, size_t k) {
+    if (!need(k)) return false;
+    off = at;
+    at += k;
+    return true;
+  };
+  auto vec = [&](uint64_t& off, uint64_t& count, size_t each) {
+    if (!need(8)) return false;
+    count = Reader{p, bytes}.u64(at);
+    at += 8;
+    if (count > (bytes - at) / each) { dg16::codec_error_text() = "key file truncated (vector length exceeds the file)"; return false; }
+    off = at;
+    at += (size_t)count * each;
+    return true;
+  };
+  bool ok = fixed(out->off_alpha_g1, 32) && fixed(out->off_beta_g2, 64) && fixed(out->off_gamma_g2, 64) &&
+            fixed(out->off_delta_g2, 64) && vec(out->off_ic, out->n_ic, 32);
+  if (ok && !verifying_key_only)
+    ok = fixed(out->off_beta_g1, 32) && fixed(out->off_delta_g1, 32) && vec(out->off_a, out->n_a, 32) &&
+         vec(out->off_b1, out->n_b1, 32) && vec(out->off_b2, out->n_b2, 64) && vec(out->off_h, out->n_h, 32) &&
+         vec(out->off_l, out->n_l, 32);
+  if (!ok) return DG16_ERR_BAD_ARG;
+  if (at != bytes) { dg16::codec_error_text() = "trailing bytes after the key"; return DG16_ERR_BAD_ARG; }
+  out->bytes = at;
+  return DG16_OK;
+}
 
 }  // extern "C"

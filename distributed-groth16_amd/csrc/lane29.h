@@ -446,6 +446,7 @@ __device__ __forceinline__ void rows_to_all32(uint32_t r, uint32_t& r0, uint32_t
 template <class P_>
 struct Fq9 {
   using P = P_;
+  static constexpr bool ORDER_TWO_POINT = HasOrderTwoPoint<Fp<P>>::value;
   static constexpr bool EXT = false;
   static constexpr int WORDS = N;
   using E = uint32_t;
@@ -514,6 +515,7 @@ struct E2 {
 template <class P_>
 struct Fq9x2 {
   using P = P_;
+  static constexpr bool ORDER_TWO_POINT = HasOrderTwoPoint<Fp2<Fp<P>>>::value;
   static_assert(Fq2Beta<P>::value == 1, "u^2 = -1");
   static constexpr bool EXT = true;
   static constexpr int WORDS = 2 * N;
@@ -755,6 +757,7 @@ __device__ __forceinline__ E14 mul(const KT& k, E14 a, E14 b) {
 template <class P_>
 struct Fq14 {
   using P = P_;
+  static constexpr bool ORDER_TWO_POINT = HasOrderTwoPoint<Fp<P>>::value;
   static constexpr bool EXT = false;
   static constexpr int WORDS = l14::N;
   using E = l14::E14;
@@ -840,6 +843,7 @@ struct E14x2 {
 template <class P_>
 struct Fq14x2 {
   using P = P_;
+  static constexpr bool ORDER_TWO_POINT = HasOrderTwoPoint<Fp2<Fp<P>>>::value;
   static constexpr bool EXT = true;
   static constexpr int BETA = Fq2Beta<P>::value;
   static constexpr int WORDS = 2 * l14::N;
@@ -1017,6 +1021,9 @@ __device__ __forceinline__ Pt<FO> dbl_pt(const typename FO::KT& k, const Pt<FO>&
   const E r2 = FO::mul(k, a2, b2);
   E w, s, mm, zz3;
   FO::rows_to_all(r2, w, s, mm, zz3);
+  if constexpr (FO::ORDER_TWO_POINT) {          // (ec29.h: HasOrderTwoPoint) y = 0: 2 p is the identity, and says so in its flag
+    if (FO::is_zero(k, zz3)) return inf_pt<FO>(k);     // zz3 = zz (2 y)^2 is a product: below 3.3 p, inside is_zero's range
+  }
   const E x3 = FO::template sub<1>(k, mm, FO::dbl_raw(s));
   const E sx = FO::template sub<3>(k, s, x3);
   // level 3: (s - x3) m | w y | zzz3 = zzz w

@@ -354,6 +354,7 @@ msm_accumulate_lds_kernel(MsmBases bases, size_t n, MsmGeom g,
       if (is_zero(r_)) {
         const XYZZ29<F> d = XYZZ29<F>::dbl_affine(q.x, qy);
         st(0, d.x); st(1, d.y); st(2, d.zz); st(3, d.zzz);
+        if constexpr (HasOrderTwoPoint<F>::value) inf = d.is_inf();     // (ec29.h) twice the point of order two
       } else {
         inf = true;
       }

@@ -302,6 +302,7 @@ msm_accumulate_steps_kernel(MsmBases bases, size_t n, MsmGeom g,
       const auto qy2 = select(negate, nq2, q2.y.template as<decltype(nq2)::Bound, decltype(nq2)::Limb>());
       const XYZZ29<F> d = XYZZ29<F>::dbl_affine(q2.x, qy2);
       st(0, d.x); st(1, d.y); st(2, d.zz); st(3, d.zzz);
+      if constexpr (HasOrderTwoPoint<F>::value) inf = d.is_inf();       // (ec29.h) twice the point of order two
     } else if (special == 2) {
       inf = true;
     }

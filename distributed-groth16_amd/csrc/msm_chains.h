@@ -227,6 +227,9 @@ __device__ __forceinline__ XYZZ29<F> dbl_wave29(const XYZZ29<F>& p) {
   if (p.is_inf()) return p;
   const unsigned slot = (__lane_id() & 15) >> 2;     // four slots per row of 16 lanes (the same in every row)
   const auto u = fit<BS>(dbl(p.y));
+  if constexpr (HasOrderTwoPoint<F>::value) {          // (ec29.h) 2 T = the identity, with zero limbs
+    if (is_zero_up_to_bound(u)) return XYZZ29<F>::inf();
+  }
   // level 1: v = u^2 | xx = x^2
   const auto a1 = select(slot == 0, u, p.x);
   const auto r1 = M::mul(a1, a1);

@@ -221,6 +221,54 @@ extern "C" int ha_point_op29(int curve, int group, int op, const void* a, const 
   return 0;
 }
 
+// ---- BLS12-377 G1's point of order two T = (q - 1, 0) through every doubling of ec29.h ------------------------------------
+// The identity of an XYZZ29 is told by zz with all limbs zero.  Returns a bit per form that must give the IDENTITY BY THAT
+// TEST (the conversions out of the representation reduce zz and would hide a zz = k p): T + T and (-T) + (-T) -- the
+// negative of y = 0 is K p, not zero limbs -- through madd, add, dbl_pt, add_mem, dbl_mem, add_acc, add_into; bit 16 says
+// that P + 2 (-T) is still P for another point P of the curve (given in a).  All set: 0x1ffff.
+extern "C" unsigned ha_order_two_29(const void* a) {
+  using F = b377_fq;
+  using FO = FieldOf<F>;
+  Affine<F> t;
+  t.x = F::one().neg();
+  t.y = F::zero();
+  uint32_t w[2 * FO::WORDS], wp[2 * FO::WORDS];
+  affine_to_internal(t, w);
+  Affine<F> pa;
+  memcpy(&pa, a, sizeof(pa));
+  affine_to_internal(pa, wp);
+  const Affine29<F> T = Affine29<F>::load(w), P = Affine29<F>::load(wp);
+  const XYZZ29<F> pos = XYZZ29<F>::inf().madd(T, false), neg_ = XYZZ29<F>::inf().madd(T, true);
+  struct Acc {
+    XYZZ29<F>* p;
+    typename FO::Store get(int c) const { return c == 0 ? p->x : c == 1 ? p->y : c == 2 ? p->zz : p->zzz; }
+    void put(int c, const typename FO::Store& v) const { (c == 0 ? p->x : c == 1 ? p->y : c == 2 ? p->zz : p->zzz) = v; }
+  };
+  unsigned ok = 0;
+  int bit = 0;
+  for (int s = 0; s < 2; s++) {
+    const XYZZ29<F> v = s ? neg_ : pos;
+    XYZZ29<F> o = v, m1, m2, a1 = v, a2 = v;
+    ok |= (unsigned)v.madd(T, s != 0).is_inf() << bit++;
+    ok |= (unsigned)v.add(o).is_inf() << bit++;
+    ok |= (unsigned)v.dbl_pt().is_inf() << bit++;
+    XYZZ29<F>::add_mem(&m1, &v, &o);
+    ok |= (unsigned)m1.is_inf() << bit++;
+    XYZZ29<F>::dbl_mem(&m2, &v);
+    ok |= (unsigned)m2.is_inf() << bit++;
+    XYZZ29<F>::add_acc(Acc{&a1}, Acc{&a1}, Acc{&o});
+    ok |= (unsigned)a1.is_inf() << bit++;
+    XYZZ29<F>::add_into(Acc{&a2}, Acc{&o});
+    ok |= (unsigned)a2.is_inf() << bit++;
+    ok |= (unsigned)XYZZ29<F>::dbl_affine(T.x, v.y).is_inf() << bit++;
+  }
+  const XYZZ29<F> p = XYZZ29<F>::inf().madd(P, false);
+  XYZZ<F> s32 = p.add(neg_.dbl_pt()).to_xyzz32();
+  const Affine<F> back = s32.to_affine();
+  ok |= (unsigned)(back.x == pa.x && back.y == pa.y) << bit;
+  return ok;
+}
+
 // ---- the constants fp29.h derives at compile time, dumped for tests/test_constants_independent.py ------------------------
 template <class P> static size_t rr_dump(uint32_t* o, size_t cap) {
   using T = RR<P>;

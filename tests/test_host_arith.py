@@ -35,6 +35,8 @@ def ha():
     L.ha_glv_split4.argtypes = [i, vp, vp, vp, vp, vp, sz]
     L.ha_canon29.argtypes = [i, i, vp, vp, vp, sz]
     L.ha_rr_consts.argtypes = [i, vp, sz]
+    L.ha_order_two_29.argtypes = [vp]
+    L.ha_order_two_29.restype = ctypes.c_uint
     return L
 
 
@@ -64,6 +66,16 @@ def test_field_ops(ha, curve, kind):
     out = np.empty_like(A)
     ha.ha_field_op(corc.fid(curve, kind), corc.OPS["to_mont"], _p(canon), _p(canon), _p(out), n)
     assert np.array_equal(out, A)
+
+
+def test_order_two_point_doubles_to_the_identity(ha):
+    """BLS12-377 G1 has a point of order two, T = (q - 1, 0) -- the only group here with a y = 0.  Every doubling of ec29.h
+    (through madd, add, add_mem, add_acc, add_into, dbl_pt, dbl_mem, dbl_affine) must turn T + T, and (-T) + (-T) where
+    y is the non-canonical zero K p, into the identity AS THE REPRESENTATION TELLS IT (zz with all limbs zero), and a
+    point plus that identity must be the point.  An MSM over T with equal scalars lost its other buckets' points this
+    way (tests/test_gpu_codec_edges.py: the order-two point in an MSM)."""
+    P = corc.gen_points("bls12_377", 1, 5, 1)
+    assert ha.ha_order_two_29(_p(P)) == 0x1FFFF
 
 
 @pytest.mark.parametrize("curve,group", [("bn254", 1), ("bn254", 2), ("bls12_381", 1),
