@@ -96,3 +96,92 @@ where
         l_query: unpack_affine::<P1>(&l),
     })
 }
+
+/// A structured reference string for the domain of size `lag_g1.len()`: the Lagrange-basis points of a powers-of-tau
+/// ceremony (include/dg16.h names the sections of a prepared `.ptau` file).  The caller vouches that every point is on
+/// its curve and of order r.
+pub struct Srs<E: Pairing> {
+    pub lag_g1: Vec<E::G1Affine>,
+    pub lag_g2: Vec<E::G2Affine>,
+    pub alpha_lag_g1: Vec<E::G1Affine>,
+    pub beta_lag_g1: Vec<E::G1Affine>,
+    /// the h basis of the reduction the key will be proved with, delta = 1 (copied to `h_query`)
+    pub h_g1: Vec<E::G1Affine>,
+    pub alpha_g1: E::G1Affine,
+    pub beta_g1: E::G1Affine,
+    pub g1: E::G1Affine,
+    pub beta_g2: E::G2Affine,
+    pub g2: E::G2Affine,
+}
+
+/// The key of `m` computed in the exponent from `srs` (`dg16_groth16_setup_srs`): gamma = delta = 1, no trapdoor.
+/// `in_subgroup` passes DG16_F_BASES_IN_SUBGROUP (the endomorphism split of the coefficients).
+pub fn setup_from_srs<E, P1, P2>(m: &ConstraintMatrices<E::ScalarField>, srs: &Srs<E>, in_subgroup: bool)
+    -> Result<ProvingKey<E>, Dg16Error>
+where
+    E: Pairing<G1Affine = Affine<P1>, G2Affine = Affine<P2>>,
+    P1: Dg16Config<ScalarField = E::ScalarField>,
+    P2: Dg16Config<ScalarField = E::ScalarField>,
+    P1::BaseField: FieldBytes,
+    P2::BaseField: FieldBytes,
+{
+    let (nc, ni) = (m.num_constraints, m.num_instance_variables);
+    let nv = ni + m.num_witness_variables;
+    let log_m = (nc + ni).next_power_of_two().trailing_zeros();
+    let domain = 1usize << log_m;
+    for n in [srs.lag_g1.len(), srs.lag_g2.len(), srs.alpha_lag_g1.len(), srs.beta_lag_g1.len(), srs.h_g1.len()] {
+        if n != domain {
+            return Err(Dg16Error::Status(sys::DG16_ERR_BAD_ARG, "the reference string is for another domain size".into()));
+        }
+    }
+    let (l1, l2) = (pack_affine(&srs.lag_g1), pack_affine(&srs.lag_g2));
+    let (al, bl, hb) = (pack_affine(&srs.alpha_lag_g1), pack_affine(&srs.beta_lag_g1), pack_affine(&srs.h_g1));
+    let fixed_in = {
+        let mut f = pack_affine(&[srs.alpha_g1, srs.beta_g1, srs.g1]);
+        f.extend(pack_affine(&[srs.beta_g2, srs.g2]));
+        f
+    };
+    let raw = sys::Dg16Srs {
+        lag_g1: l1.as_ptr().cast(),
+        lag_g2: l2.as_ptr().cast(),
+        alpha_lag_g1: al.as_ptr().cast(),
+        beta_lag_g1: bl.as_ptr().cast(),
+        h_g1: hb.as_ptr().cast(),
+        fixed: fixed_in.as_ptr().cast(),
+    };
+    let (ca, cb, cc) = (Csr::from_rows(&m.a), Csr::from_rows(&m.b), Csr::from_rows(&m.c));
+    let (f1, f2) = (2 * <P1::BaseField as FieldBytes>::BYTES, 2 * <P2::BaseField as FieldBytes>::BYTES);
+    let (mut a, mut b1, mut b2) = (vec![0u8; nv * f1], vec![0u8; nv * f1], vec![0u8; nv * f2]);
+    let (mut h, mut l) = (vec![0u8; domain * f1], vec![0u8; (nv - ni) * f1]);
+    let (mut fixed, mut gamma_g2, mut ic) = (vec![0u8; 3 * f1 + 2 * f2], vec![0u8; f2], vec![0u8; ni * f1]);
+    check(unsafe {
+        sys::dg16_groth16_setup_srs(
+            CTX.0, P1::CURVE, nc, ni, nv, log_m,
+            ca.row_ptr.as_ptr(), ca.col.as_ptr(), scalars_as_bytes(&ca.coeff).as_ptr().cast(),
+            cb.row_ptr.as_ptr(), cb.col.as_ptr(), scalars_as_bytes(&cb.coeff).as_ptr().cast(),
+            cc.row_ptr.as_ptr(), cc.col.as_ptr(), scalars_as_bytes(&cc.coeff).as_ptr().cast(),
+            &raw, a.as_mut_ptr().cast(), b1.as_mut_ptr().cast(), b2.as_mut_ptr().cast(), h.as_mut_ptr().cast(),
+            l.as_mut_ptr().cast(), fixed.as_mut_ptr().cast(), gamma_g2.as_mut_ptr().cast(), ic.as_mut_ptr().cast(),
+            if in_subgroup { sys::DG16_F_BASES_IN_SUBGROUP } else { 0 },
+        )
+    })?;
+    let g1_fixed = unpack_affine::<P1>(&fixed[..3 * f1]);
+    let g2_fixed = unpack_affine::<P2>(&fixed[3 * f1..]);
+    let vk = VerifyingKey::<E> {
+        alpha_g1: g1_fixed[0],
+        beta_g2: g2_fixed[0],
+        gamma_g2: unpack_affine::<P2>(&gamma_g2)[0],
+        delta_g2: g2_fixed[1],
+        gamma_abc_g1: unpack_affine::<P1>(&ic),
+    };
+    Ok(ProvingKey::<E> {
+        vk,
+        beta_g1: g1_fixed[1],
+        delta_g1: g1_fixed[2],
+        a_query: unpack_affine::<P1>(&a),
+        b_g1_query: unpack_affine::<P1>(&b1),
+        b_g2_query: unpack_affine::<P2>(&b2),
+        h_query: unpack_affine::<P1>(&h),
+        l_query: unpack_affine::<P1>(&l),
+    })
+}

@@ -131,6 +131,17 @@ pub struct Dg16Csr {
     pub col: *const u32,
     pub coeff: *const c_void,
 }
+/// `dg16_srs`: the reference string of `dg16_groth16_setup_srs` (five arrays of m affine points; `fixed` is a HOST pointer)
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct Dg16Srs {
+    pub lag_g1: *const c_void,
+    pub lag_g2: *const c_void,
+    pub alpha_lag_g1: *const c_void,
+    pub beta_lag_g1: *const c_void,
+    pub h_g1: *const c_void,
+    pub fixed: *const c_void,
+}
 /// `dg16_arkkey_layout_t`
 #[repr(C)]
 #[derive(Clone, Copy, Debug, Default)]
@@ -203,6 +214,15 @@ extern "C" {
                     b_g2_query: *mut c_void, h_query: *mut c_void, l_query: *mut c_void,
                     fixed_points: *mut c_void, gamma_g2: *mut c_void, gamma_abc_g1: *mut c_void,
                     flags: c_uint) -> c_int;
+    // the same key in the exponent, from the Lagrange-basis points of a powers-of-tau ceremony (gamma = delta = 1)
+    pub fn dg16_groth16_setup_srs(ctx: *mut Dg16Ctx, curve: c_int, num_constraints: usize, num_inputs: usize,
+                    num_vars: usize, log_m: c_uint, a_row_ptr: *const u32, a_col: *const u32,
+                    a_coeff: *const c_void, b_row_ptr: *const u32, b_col: *const u32, b_coeff: *const c_void,
+                    c_row_ptr: *const u32, c_col: *const u32, c_coeff: *const c_void, srs: *const Dg16Srs,
+                    a_query: *mut c_void, b_g1_query: *mut c_void, b_g2_query: *mut c_void, h_query: *mut c_void,
+                    l_query: *mut c_void, fixed_points: *mut c_void, gamma_g2: *mut c_void,
+                    gamma_abc_g1: *mut c_void, flags: c_uint) -> c_int;
+    pub fn dg16_setup_srs_limits(wave_from: *mut c_uint, msm_from: *mut c_uint);
     pub fn dg16_to_affine(ctx: *mut Dg16Ctx, curve: c_int, group: c_int, jac: *const c_void, out: *mut c_void,
                           n: usize, flags: c_uint, channel: c_int) -> c_int;
     // resident bases (a CRS is uploaded once; msm over its window tables)

@@ -18,4 +18,5 @@ from .lib import (  # noqa: F401
     F_OUT_AFFINE,
 )
 from .keygen import generate_parameters, Parameters  # noqa: F401,E402
+from .keygen import generate_parameters_from_srs, srs_from_trapdoor, Srs  # noqa: F401,E402
 from .verify import PreparedVerifyingKey  # noqa: F401,E402

@@ -4,7 +4,8 @@
 //
 //   u = L_i(tau), i < m        inverse NTT of [tau^j]: L_i(tau) = (1/m) sum_j (tau w^-i)^j
 //   a_k, b_k, c_k = (M^T u)_k  the three CSR matrices are transposed by a counting sort over the columns (count,
-//                              scan, fill); one lane per wire then GATHERS its column -- there is no atomic add in Fr
+//                              scan, fill: setup_transpose.h); one lane per wire then GATHERS its column -- there
+//                              is no atomic add in Fr
 //   abc_k = beta a_k + alpha b_k + c_k, / gamma for the instance wires, / delta for the witness wires
 //   h                          inverse NTT of size 2 m of [tau^j / delta]_{j < 2m-1} | 0, odd-indexed entries
 //                              (DG16_F_QAP_LIBSNARK: the geometric sequence tau^i Z(tau) / delta, i < m - 1, then 0)
@@ -13,6 +14,7 @@
 
 #include "fixed_base_impl.h"
 #include "setup.h"
+#include "setup_transpose.h"
 
 #ifndef DG_CURVE
 #error "compile with -DDG_CURVE=<curve id>"
@@ -23,15 +25,6 @@ namespace {
 
 using CT = CurveTypes<DG_CURVE>;
 using Fr = CT::Fr;
-
-struct DevBuf {     // temporary device memory of one setup call (hipFree waits for the kernels that use it)
-  void* p = nullptr;
-  explicit DevBuf(size_t bytes) { DG_HIP(hipMalloc(&p, bytes ? bytes : 16)); }
-  ~DevBuf() { if (p) (void)hipFree(p); }
-  DevBuf(const DevBuf&) = delete;
-  DevBuf& operator=(const DevBuf&) = delete;
-  template <class T> T* as() const { return (T*)p; }
-};
 
 // out[j] = scale * base^j for j < count, zero for count <= j < total
 __global__ void __launch_bounds__(256) setup_powers_kernel(Fr* __restrict__ out, size_t count, size_t total,
@@ -61,78 +54,7 @@ __global__ void __launch_bounds__(256) setup_odd_kernel(const Fr* __restrict__ i
   if (i < m) out[i] = in[2 * i + 1];
 }
 
-// A row whose pointers are not ordered or reach beyond nnz, and an entry whose column is not a wire, are skipped and
-// reported (flag): nothing is read or written out of range.  The same rule in the count and the fill pass.
-__device__ __forceinline__ bool setup_row(const unsigned* row_ptr, size_t i, size_t nnz, unsigned& lo, unsigned& hi,
-                                          unsigned* flag) {
-  lo = row_ptr[i];
-  hi = row_ptr[i + 1];
-  if (hi < lo || hi > nnz) {
-    *flag = 1u;
-    return false;
-  }
-  return true;
-}
-__global__ void __launch_bounds__(256) setup_count_kernel(const unsigned* __restrict__ row_ptr,
-                                                           const unsigned* __restrict__ col, size_t nc, size_t nv,
-                                                           size_t nnz, unsigned* __restrict__ counts, unsigned* flag) {
-  size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= nc) return;
-  unsigned lo, hi;
-  if (!setup_row(row_ptr, i, nnz, lo, hi, flag)) return;
-  for (unsigned j = lo; j < hi; j++) {
-    const unsigned cl = col[j];
-    if (cl >= nv) { *flag = 1u; continue; }
-    atomicAdd(&counts[cl], 1u);
-  }
-}
-// ptr[k] = cursor[k] = sum of counts[0..k), ptr[n] = total; one workgroup
-__global__ void __launch_bounds__(1024) setup_scan_kernel(const unsigned* __restrict__ counts, size_t n,
-                                                           unsigned* __restrict__ ptr, unsigned* __restrict__ cursor) {
-  __shared__ unsigned sums[1024];
-  const unsigned tid = threadIdx.x;
-  const size_t per = (n + 1023) / 1024;
-  const size_t lo = tid * per < n ? tid * per : n, hi = lo + per < n ? lo + per : n;
-  unsigned s = 0;
-  for (size_t i = lo; i < hi; i++) s += counts[i];
-  sums[tid] = s;
-  __syncthreads();
-  for (unsigned off = 1; off < 1024; off <<= 1) {
-    const unsigned v = tid >= off ? sums[tid - off] : 0u;
-    __syncthreads();
-    sums[tid] += v;
-    __syncthreads();
-  }
-  unsigned run = tid ? sums[tid - 1] : 0u;
-  for (size_t i = lo; i < hi; i++) {
-    ptr[i] = run;
-    cursor[i] = run;
-    run += counts[i];
-  }
-  if (tid == 1023) ptr[n] = sums[1023];
-}
-__global__ void __launch_bounds__(256) setup_fill_kernel(const unsigned* __restrict__ row_ptr,
-                                                          const unsigned* __restrict__ col, size_t nc, size_t nv,
-                                                          size_t nnz, unsigned* __restrict__ cursor,
-                                                          unsigned* __restrict__ t_row, unsigned* __restrict__ t_src,
-                                                          unsigned* flag) {
-  size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= nc) return;
-  unsigned lo, hi;
-  if (!setup_row(row_ptr, i, nnz, lo, hi, flag)) return;
-  for (unsigned j = lo; j < hi; j++) {
-    const unsigned cl = col[j];
-    if (cl >= nv) continue;
-    const unsigned pos = atomicAdd(&cursor[cl], 1u);    // < ptr[cl + 1] <= nnz: the count pass saw the same entries
-    t_row[pos] = (unsigned)i;
-    t_src[pos] = j;
-  }
-}
-
-struct TCsr {      // a matrix by wire: entries ptr[k] .. ptr[k + 1) of wire k are (constraint t_row, coeff[t_src])
-  const unsigned *ptr, *t_row, *t_src;
-  const Fr* coeff;
-};
+using TCsr = TCsrT<Fr>;      // setup_transpose.h
 __device__ __forceinline__ Fr setup_column(const TCsr& M, size_t k, const Fr* __restrict__ u) {
   Fr acc = Fr::zero();
   for (unsigned p = M.ptr[k], e = M.ptr[k + 1]; p < e; p++) acc = acc + M.coeff[M.t_src[p]] * u[M.t_row[p]];
@@ -224,29 +146,8 @@ void groth16_setup_run<DG_CURVE>(Call& k, const SetupArgs& s) {
       hipLaunchKernelGGL(setup_odd_kernel, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, k.s(), big.as<Fr>(), m,
                          h_s.as<Fr>());
     }
-    // transposes: per matrix ptr[nv + 1], cursor / counts [nv], t_row, t_src [nnz]
-    DevBuf counts(3 * nv * sizeof(unsigned)), cursor(3 * nv * sizeof(unsigned)), ptr(3 * (nv + 1) * sizeof(unsigned));
-    DevBuf trow((s.nnz[0] + s.nnz[1] + s.nnz[2]) * sizeof(unsigned)), tsrc((s.nnz[0] + s.nnz[1] + s.nnz[2]) * sizeof(unsigned));
-    DG_HIP(hipMemsetAsync(counts.p, 0, 3 * nv * sizeof(unsigned), k.s()));
-    TCsr t[3];
-    size_t off = 0;
-    for (int j = 0; j < 3; j++) {
-      unsigned* cnt = counts.as<unsigned>() + j * nv;
-      unsigned* cur = cursor.as<unsigned>() + j * nv;
-      unsigned* p = ptr.as<unsigned>() + j * (nv + 1);
-      unsigned* tr = trow.as<unsigned>() + off;
-      unsigned* tsr = tsrc.as<unsigned>() + off;
-      off += s.nnz[j];
-      const unsigned blocks = (unsigned)((nc + 255) / 256);
-      if (nc)
-        hipLaunchKernelGGL(setup_count_kernel, dim3(blocks), dim3(256), 0, k.s(), s.row_ptr[j], s.col[j], nc, nv,
-                           s.nnz[j], cnt, flag);
-      hipLaunchKernelGGL(setup_scan_kernel, dim3(1), dim3(1024), 0, k.s(), cnt, nv, p, cur);
-      if (nc)
-        hipLaunchKernelGGL(setup_fill_kernel, dim3(blocks), dim3(256), 0, k.s(), s.row_ptr[j], s.col[j], nc, nv,
-                           s.nnz[j], cur, tr, tsr, flag);
-      t[j] = TCsr{p, tr, tsr, (const Fr*)s.coeff[j]};
-    }
+    Transposes<Fr> tr(k, s.row_ptr, s.col, s.coeff, s.nnz, nc, nv, flag);
+    const TCsr* t = tr.t;
     hipLaunchKernelGGL(setup_wire_kernel, dim3((unsigned)((nv + 255) / 256)), dim3(256), 0, k.s(), t[0], t[1], t[2],
                        u.as<Fr>(), cd, nc, ni, nv, a_s.as<Fr>(), b_s.as<Fr>(), gabc_s.as<Fr>(), l_s.as<Fr>());
     DG_HIP(hipGetLastError());

@@ -6,6 +6,11 @@
     pk = params.proving_key(ctx)                              # resident key (dg16_pk_create on device pointers)
     ok = verify.verify_proof(*params.verifying_key(), public_inputs, proof_affine)
 
+A key nobody holds the trapdoor of is computed in the exponent, from the Lagrange-basis points of a powers-of-tau
+ceremony (`dg16_groth16_setup_srs`, csrc/setup_srs_curve.hip); it has gamma = delta = 1:
+
+    params = generate_parameters_from_srs(ctx, "bn254", r1cs, srs)      # srs: an Srs, e.g. decoded from a prepared .ptau
+
 The trapdoor (alpha, beta, gamma, delta, tau) is drawn from `secrets` unless the caller passes one; it is returned with
 the parameters only when it was passed in.  torch is the device-memory plumbing; there is no CPU path."""
 
@@ -174,5 +179,123 @@ def generate_parameters(ctx, curve, r1cs, trapdoor=None, generators=None, reduct
     ctx.groth16_setup(curve, nc, ni, nv, log_m, *[[t.data_ptr() for t in m] for m in mats], p["trapdoor"],
                       [t.data_ptr() for t in arrays], generators=gens, device_ptrs=True, reduction=reduction)
     params = Parameters(curve, nc, ni, nv, log_m, arrays, trapdoor=tuple(trapdoor) if p["trapdoor_given"] else None)
+    params.reduction = reduction
+    return params
+
+
+class Srs:
+    """A structured reference string for the domain of size 2^log_m, as `dg16_groth16_setup_srs` takes it: lag_g1,
+    lag_g2, alpha_lag_g1, beta_lag_g1, h_g1 -- 2^log_m affine points each (numpy uint64 arrays, or device tensors; identity
+    = zeros) -- and fixed = alpha_g1 | beta_g1 | g1 | beta_g2 | g2 (host array).  include/dg16.h names the sections of a
+    prepared .ptau file they come from.  The points must be on their curves and of order r: nothing here checks that."""
+
+    ARRAYS = ("lag_g1", "lag_g2", "alpha_lag_g1", "beta_lag_g1", "h_g1")
+
+    def __init__(self, curve, log_m, lag_g1, lag_g2, alpha_lag_g1, beta_lag_g1, h_g1, fixed, reduction=None):
+        self.curve, self.log_m, self.reduction = curve, log_m, reduction
+        self.lag_g1, self.lag_g2, self.alpha_lag_g1, self.beta_lag_g1, self.h_g1 = \
+            lag_g1, lag_g2, alpha_lag_g1, beta_lag_g1, h_g1
+        self.fixed = np.ascontiguousarray(fixed, dtype=np.uint64).reshape(-1)
+        fq = _lib.FQ_LIMBS64[curve]
+        if self.fixed.size != 3 * 2 * fq + 2 * 4 * fq:
+            raise ValueError("fixed = alpha_g1 | beta_g1 | g1 | beta_g2 | g2")
+
+
+def _ints_to_arr(vals):
+    return np.frombuffer(b"".join(int(v).to_bytes(32, "little") for v in vals), dtype=np.uint64).reshape(-1, 4).copy()
+
+
+def srs_scalars(ctx, curve, log_m, tau, reduction="circom"):
+    """(u, h) as canonical uint64 [m][4] arrays, made the way dg16_groth16_setup makes them, with delta = 1:
+    u_i = L_i(tau) is the inverse NTT of [tau^j]; h is, for "circom", the odd-indexed entries of the inverse NTT of size
+    2m of [tau^j]_{j < 2m - 1} | 0 and, for "libsnark", tau^i Z(tau) for i < m - 1, then 0."""
+    _lib._reduction_flag(reduction)
+    r = FR_MODULUS[curve]
+    m = 1 << log_m
+    pw = [1] * (2 * m)
+    for j in range(1, 2 * m):
+        pw[j] = pw[j - 1] * tau % r
+    u = ctx.ntt(curve, _ints_to_arr(pw[:m]), inverse=True)
+    if reduction == "libsnark":
+        z = (pw[m] - 1) % r
+        h = _ints_to_arr([pw[i] * z % r for i in range(m - 1)] + [0])
+    else:
+        h = ctx.ntt(curve, _ints_to_arr(pw[:2 * m - 1] + [0]), inverse=True)[1::2].copy()
+    return u, h
+
+
+def srs_from_trapdoor(ctx, curve, log_m, alpha, beta, tau, reduction="circom"):
+    """FOR TESTS AND BENCHMARKS ONLY: the reference string a ceremony with the KNOWN secrets alpha, beta, tau would
+    publish, over the standard generators.  A key made from it is as worthless as its trapdoor is public; a real one
+    comes from a ceremony's output.  The five arrays are dg16_fixed_base_mul products of the scalars of srs_scalars
+    (which stay on the result as `u` and `h`, canonical, for a test to check).  Host arrays."""
+    r = FR_MODULUS[curve]
+    alpha, beta, tau = int(alpha), int(beta), int(tau)
+    if any(not 0 < x < r for x in (alpha, beta, tau)) or pow(tau, 1 << log_m, r) == 1:
+        raise ValueError("alpha, beta, tau must be non-zero and below r, tau outside the domain")
+    if log_m + 1 > TWO_ADICITY[curve] or log_m > 26:
+        raise ValueError("domain larger than the field's 2-adic subgroup")
+    u, h = srs_scalars(ctx, curve, log_m, tau, reduction)
+    ab = ctx.fixed_base_mul(curve, 1, _ints_to_arr([alpha, beta, 1]))
+    b2 = ctx.fixed_base_mul(curve, 2, _ints_to_arr([beta, 1]))
+    srs = Srs(curve, log_m, ctx.fixed_base_mul(curve, 1, u), ctx.fixed_base_mul(curve, 2, u),
+              ctx.fixed_base_mul(curve, 1, u, base=ab[0]), ctx.fixed_base_mul(curve, 1, u, base=ab[1]),
+              ctx.fixed_base_mul(curve, 1, h), np.concatenate([ab.reshape(-1), b2.reshape(-1)]), reduction=reduction)
+    srs.u, srs.h = u, h
+    return srs
+
+
+def generate_parameters_from_srs(ctx, curve, r1cs, srs, reduction="circom", in_subgroup=False):
+    """The key of `r1cs` from a structured reference string (an Srs for the domain of the system: log_m must match), in
+    the exponent: gamma = delta = 1 and no trapdoor anywhere.  reduction names the QAP reduction srs.h_g1 was made for
+    (it is recorded on the result; prove with the same one).  in_subgroup=True passes DG16_F_BASES_IN_SUBGROUP: the
+    caller vouches that every point of the string has order r, and the coefficients may then be split with the curve's
+    endomorphism.  Returns Parameters (trapdoor None); proving_key() and verifying_key() work as for generate_parameters."""
+    _lib._reduction_flag(reduction)
+    if srs.reduction is not None and srs.reduction != reduction:
+        raise ValueError("the reference string's h basis was made for reduction %r" % (srs.reduction,))
+    p = prepare(curve, r1cs, trapdoor=(1, 1, 1, 1, 2))       # shapes and CSR validation only: no trapdoor is used
+    if srs.curve != curve or srs.log_m != p["log_m"]:
+        raise ValueError("the reference string is for %s, 2^%d; the system needs %s, 2^%d"
+                         % (srs.curve, srs.log_m, curve, p["log_m"]))
+    if ctx is None:
+        ctx = _lib.Context(0)
+    import torch
+    dev = torch.device("cuda", ctx.device)
+    nc, ni, nv, log_m = p["nc"], p["ni"], p["nv"], p["log_m"]
+    m = 1 << log_m
+
+    def up(x, dtype=np.uint64):
+        if _is_tensor(x):
+            return x
+        x = np.ascontiguousarray(x, dtype=dtype)
+        if x.size == 0:
+            return torch.zeros(16, dtype=torch.uint8, device=dev)
+        return torch.from_numpy(x.view(np.uint8).reshape(-1)).to(dev)
+
+    mats = []
+    for ptr, col, coeff in p["csr"]:
+        d = (up(ptr, np.uint32), up(col, np.uint32), up(coeff))
+        if not p["coeff_mont"]:
+            nnz = d[2].numel() * d[2].element_size() // 32
+            if _is_tensor(coeff):
+                d = (d[0], d[1], d[2].clone())
+            torch.cuda.synchronize(dev)
+            ctx.field_op_dev(curve, "fr", 5, d[2].data_ptr(), None, d[2].data_ptr(), nnz)      # to Montgomery form
+        mats.append(d)
+    fqb = 8 * _lib.FQ_LIMBS64[curve]
+    g1b, g2b = 2 * fqb, 4 * fqb
+    tabs = [up(getattr(srs, n)) for n in Srs.ARRAYS]
+    for t, n, b in zip(tabs, Srs.ARRAYS, (g1b, g2b, g1b, g1b, g1b)):
+        if t.numel() * t.element_size() != m * b:
+            raise ValueError("srs.%s must hold 2^%d points" % (n, log_m))
+    sizes = (nv * g1b, nv * g1b, nv * g2b, m * g1b, (nv - ni) * g1b, 3 * g1b + 2 * g2b, g2b, ni * g1b)
+    arrays = [torch.empty(max(s, 16), dtype=torch.uint8, device=dev)[:s] for s in sizes]
+    torch.cuda.synchronize(dev)        # the uploads ran on torch's stream, the generator runs on the library's
+    ctx.sync(0)
+    ctx.groth16_setup_srs(curve, nc, ni, nv, log_m, *[[t.data_ptr() for t in mt] for mt in mats],
+                          [t.data_ptr() for t in tabs] + [srs.fixed], [t.data_ptr() for t in arrays], device_ptrs=True,
+                          in_subgroup=in_subgroup)
+    params = Parameters(curve, nc, ni, nv, log_m, arrays, trapdoor=None)
     params.reduction = reduction
     return params

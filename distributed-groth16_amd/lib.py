@@ -53,6 +53,10 @@ class ZkeyHeader(ctypes.Structure):       # dg16_zkey_header
     _fields_ = [(n, ctypes.c_uint32) for n in ("n_vars", "n_public", "domain_size", "num_constraints")]
 
 
+class Srs(ctypes.Structure):              # dg16_srs
+    _fields_ = [(n, ctypes.c_void_p) for n in ("lag_g1", "lag_g2", "alpha_lag_g1", "beta_lag_g1", "h_g1", "fixed")]
+
+
 class PkInfo(ctypes.Structure):           # dg16_pk_info
     _fields_ = [("n_ab", ctypes.c_uint64), ("n_l", ctypes.c_uint64), ("n_h", ctypes.c_uint64),
                 ("c_ab", ctypes.c_uint32), ("c_l", ctypes.c_uint32), ("c_h", ctypes.c_uint32),
@@ -151,6 +155,9 @@ def load():
     L.dg16_fixed_base_window_bits.argtypes = [sz]
     L.dg16_fixed_base_window_bits.restype = u
     L.dg16_groth16_setup.argtypes = [vp, i, sz, sz, sz, u] + [vp] * 19 + [u]
+    L.dg16_groth16_setup_srs.argtypes = [vp, i, sz, sz, sz, u] + [vp] * 9 + [ctypes.POINTER(Srs)] + [vp] * 8 + [u]
+    L.dg16_setup_srs_limits.argtypes = [ctypes.POINTER(u), ctypes.POINTER(u)]
+    L.dg16_setup_srs_limits.restype = None
     if hasattr(L, "dg16_ctx_set_table_budget"):      # (absent from older builds named by DG16_LIB for A/B timing)
         L.dg16_ctx_set_table_budget.argtypes = [vp, u64]
     L.dg16_bases_upload.argtypes = [vp, i, i, vp, sz, u, ctypes.POINTER(vp)]
@@ -278,7 +285,8 @@ EXPORTED = ["dg16_ctx_create", "dg16_ctx_destroy", "dg16_last_error", "dg16_set_
             "dg16_verify_error", "dg16_groth16_verify", "dg16_prove_a", "dg16_prove_b", "dg16_prove_c",
             "dg16_ctx_set_table_budget", "dg16_fixed_base_mul", "dg16_fixed_base_window_bits", "dg16_groth16_setup",
             "dg16_vk_create", "dg16_vk_destroy", "dg16_groth16_verify_batch", "dg16_groth16_verify_aggregate",
-            "dg16_points_mul", "dg16_ctx_set_points_mul_slice", "dg16_groth16_rerandomize"]
+            "dg16_points_mul", "dg16_ctx_set_points_mul_slice", "dg16_groth16_rerandomize",
+            "dg16_groth16_setup_srs", "dg16_setup_srs_limits"]
 
 
 def _ptr(x):
@@ -582,6 +590,27 @@ class Context:
                                             *[_ptr(x) for x in mats], _ptr(trapdoor), _ptr(generators),
                                             *[_ptr(x) for x in outputs],
                                             (F_DEVICE_PTRS if device_ptrs else 0) | _reduction_flag(reduction)))
+
+    def groth16_setup_srs(self, curve, num_constraints, num_inputs, num_vars, log_m, csr_a, csr_b, csr_c, srs, outputs,
+                          device_ptrs=False, in_subgroup=False):
+        """dg16_groth16_setup_srs.  csr_* and outputs as for groth16_setup; srs = (lag_g1, lag_g2, alpha_lag_g1,
+        beta_lag_g1, h_g1, fixed): five arrays of 2^log_m affine points (numpy arrays, or device pointers with
+        device_ptrs) and the HOST array alpha_g1 | beta_g1 | g1 | beta_g2 | g2; None passes NULL.  The caller vouches for
+        the points (on the curve, order r); in_subgroup=True then allows the endomorphism split.  Synchronous."""
+        mats = []
+        for m in (csr_a, csr_b, csr_c):
+            mats += list(m) if device_ptrs else [np.ascontiguousarray(x) for x in m]
+        s = None
+        if srs is not None:
+            arrays = list(srs[:5]) if device_ptrs else [None if x is None else np.ascontiguousarray(x) for x in srs[:5]]
+            fixed = None if srs[5] is None else np.ascontiguousarray(srs[5], dtype=np.uint64)
+            keep = (arrays, fixed, mats)          # noqa: F841 (the arrays outlive the call)
+            addr = lambda x: None if x is None else x.ctypes.data if isinstance(x, np.ndarray) else int(x)   # noqa: E731
+            s = Srs(*[addr(x) for x in arrays], addr(fixed))
+        flags = (F_DEVICE_PTRS if device_ptrs else 0) | (F_BASES_IN_SUBGROUP if in_subgroup else 0)
+        self._chk(self.L.dg16_groth16_setup_srs(self.h, CURVES[curve], num_constraints, num_inputs, num_vars, log_m,
+                                                *[_ptr(x) for x in mats], None if s is None else ctypes.byref(s),
+                                                *[_ptr(x) for x in outputs], flags))
 
     def to_affine(self, curve, group, jac, channel=0):
         jac = np.ascontiguousarray(jac, dtype=np.uint64)

@@ -255,6 +255,52 @@ int dg16_groth16_setup(dg16_ctx *ctx, int curve, size_t num_constraints, size_t 
                        void *b_g2_query, void *h_query, void *l_query, void *fixed_points, void *gamma_g2,
                        void *gamma_abc_g1, unsigned flags);
 
+/* The same key computed IN THE EXPONENT from a structured reference string: the Lagrange-basis points of a
+ * powers-of-tau ceremony for the domain of size m = 2^log_m.  Nobody holds the trapdoor; the key has gamma = delta = 1
+ * (what a snarkjs `zkey new` writes before any phase-2 contribution).  Where the arrays come from:
+ *   lag_g1, lag_g2, alpha_lag_g1, beta_lag_g1   sections 12, 13, 14, 15 of a PREPARED phase-2 .ptau file (snarkjs
+ *       `powersoftau prepare phase2`: tauG1, tauG2, alphaTauG1, betaTauG1 in Lagrange form), the block of the power
+ *       log_m in each -- decoded to this library's affine Montgomery layout.  In arkworks terms: the group inverse FFT
+ *       over Radix2EvaluationDomain::new(m) of [tau^j G], [tau^j G2], [alpha tau^j G], [beta tau^j G], j < m.
+ *   h_g1   the h basis of the QAP reduction the key will be proved with, for delta = 1.  CircomReduction: the points
+ *       L'_{2i+1}(tau) G of the size-2m Lagrange basis with odd index (snarkjs reads them from the block of the power
+ *       log_m + 1 of section 12), i < m.  LibsnarkReduction: tau^i Z(tau) G = (tau^(i+m) - tau^i) G for i < m - 1
+ *       and the identity at i = m - 1.  It is copied to h_query as it stands: deriving it from tau powers needs a
+ *       group NTT, which is not part of this call.
+ *   fixed  alpha G1, beta G1, G1, beta G2, G2: the first elements of sections 4 (alphaTauG1), 5 (betaTauG1) and 2
+ *       (tauG1), section 6 (betaG2) and the first element of section 3 (tauG2).
+ * THE CALLER GUARANTEES that every point of the reference string is on its curve and in the subgroup of order r --
+ * the call does not check either (a ceremony verifier does).  With that guarantee DG16_F_BASES_IN_SUBGROUP may be
+ * passed and allows the endomorphism split of the coefficients, exactly as for dg16_points_mul; without the flag the
+ * plain loops run, which are correct for any point of the curve. */
+typedef struct dg16_srs {          /* affine points, identity = zero bytes; device pointers iff DG16_F_DEVICE_PTRS */
+  const void *lag_g1;              /* [m]  L_i(tau) G1, the Lagrange basis of the size-m domain */
+  const void *lag_g2;              /* [m]  L_i(tau) G2 */
+  const void *alpha_lag_g1;        /* [m]  alpha L_i(tau) G1 */
+  const void *beta_lag_g1;         /* [m]  beta  L_i(tau) G1 */
+  const void *h_g1;                /* [m]  the h basis of the chosen reduction with delta = 1, copied to h_query */
+  const void *fixed;               /* HOST: alpha_g1 | beta_g1 | g1 (G1 affine) | beta_g2 | g2 (G2 affine) */
+} dg16_srs;
+
+/* A, B, C, the sizes and the eight outputs with their layouts are those of dg16_groth16_setup.  With u_i = L_i(tau):
+ *   a_query[k]    = sum over the entries (i, k, v) of A of v * lag_g1[i], + lag_g1[nc + k] for k < num_inputs
+ *   b_g1_query[k] = sum_B v * lag_g1[i];  b_g2_query[k] = sum_B v * lag_g2[i]
+ *   K_k = sum_A v * beta_lag_g1[i] (+ beta_lag_g1[nc + k] for k < num_inputs) + sum_B v * alpha_lag_g1[i]
+ *         + sum_C v * lag_g1[i];  gamma_abc_g1[k] = K_k for k < num_inputs, l_query[k - num_inputs] = K_k otherwise
+ *   h_query = h_g1;  fixed_points = alpha_g1 | beta_g1 | g1 | beta_g2 | g2;  gamma_g2 = g2.
+ * Coefficients 0, 1 and r - 1 cost no multiplication; the others go through dg16_points_mul's loops, in slices of the
+ * size dg16_ctx_set_points_mul_slice sets (0: 2^17 terms).  A wire's terms are added by one lane, by a wave (from
+ * wave_from terms) or, from msm_from terms on, by the library's MSM (dg16_setup_srs_limits reports the two thresholds).
+ * Synchronous in both pointer forms; runs on channel 0.  A matrix entry whose column is not a wire, or a row_ptr that
+ * is not ordered, is DG16_ERR_BAD_ARG, as is a NULL srs or a NULL array in it; nothing is read out of range. */
+int dg16_groth16_setup_srs(dg16_ctx *ctx, int curve, size_t num_constraints, size_t num_inputs, size_t num_vars,
+                           unsigned log_m, const uint32_t *a_row_ptr, const uint32_t *a_col, const void *a_coeff,
+                           const uint32_t *b_row_ptr, const uint32_t *b_col, const void *b_coeff,
+                           const uint32_t *c_row_ptr, const uint32_t *c_col, const void *c_coeff,
+                           const dg16_srs *srs, void *a_query, void *b_g1_query, void *b_g2_query, void *h_query,
+                           void *l_query, void *fixed_points, void *gamma_g2, void *gamma_abc_g1, unsigned flags);
+void dg16_setup_srs_limits(unsigned *wave_from, unsigned *msm_from);
+
 /* ---- Groth16 prover (single prover; the value the n-party run must equal) ------------------------
  * Replaces `Groth16::<E, CircomReduction>::create_proof_with_reduction_and_matrices` (third-party
  * fork; call sites groth16/examples/sha256.rs:159, mpc-api/src/main.rs:393) from the point where
