@@ -166,6 +166,7 @@ extern "C" {
     pub fn dg16_h_poly(ctx: *mut Dg16Ctx, curve: c_int, a: *const c_void, b: *const c_void,
                        c: *const c_void, log_m: c_uint, out: *mut c_void, flags: c_uint,
                        channel: c_int) -> c_int;
+    // with DG16_F_DEVICE_PTRS: synchronous; ordered behind the work enqueued on channel 0's stream; outputs complete on return
     pub fn dg16_pk_create(ctx: *mut Dg16Ctx, curve: c_int, num_vars: usize, num_inputs: usize,
                           domain_size: usize, a_query: *const c_void, b_g1_query: *const c_void,
                           b_g2_query: *const c_void, h_query: *const c_void, l_query: *const c_void,
@@ -206,6 +207,7 @@ extern "C" {
                                scalars: *const c_void, n: usize, out_affine: *mut c_void, flags: c_uint,
                                channel: c_int) -> c_int;
     pub fn dg16_fixed_base_window_bits(n: usize) -> c_uint;
+    // with DG16_F_DEVICE_PTRS: synchronous; ordered behind the work enqueued on channel 0's stream; outputs complete on return
     pub fn dg16_groth16_setup(ctx: *mut Dg16Ctx, curve: c_int, num_constraints: usize, num_inputs: usize,
                     num_vars: usize, log_m: c_uint, a_row_ptr: *const u32, a_col: *const u32,
                     a_coeff: *const c_void, b_row_ptr: *const u32, b_col: *const u32, b_coeff: *const c_void,
@@ -215,6 +217,7 @@ extern "C" {
                     fixed_points: *mut c_void, gamma_g2: *mut c_void, gamma_abc_g1: *mut c_void,
                     flags: c_uint) -> c_int;
     // the same key in the exponent, from the Lagrange-basis points of a powers-of-tau ceremony (gamma = delta = 1)
+    // with DG16_F_DEVICE_PTRS: synchronous; ordered behind the work enqueued on channel 0's stream; outputs complete on return
     pub fn dg16_groth16_setup_srs(ctx: *mut Dg16Ctx, curve: c_int, num_constraints: usize, num_inputs: usize,
                     num_vars: usize, log_m: c_uint, a_row_ptr: *const u32, a_col: *const u32,
                     a_coeff: *const c_void, b_row_ptr: *const u32, b_col: *const u32, b_coeff: *const c_void,
@@ -238,6 +241,7 @@ extern "C" {
                                out: *mut c_void) -> c_int;
     // keys, shards, the halves of a distributed proof
     pub fn dg16_pk_info_get(pk: *const Dg16Pk, out: *mut Dg16PkInfo) -> c_int;
+    // with DG16_F_DEVICE_PTRS: synchronous; ordered behind the work enqueued on channel 0's stream; outputs complete on return
     pub fn dg16_pk_create_shard(ctx: *mut Dg16Ctx, curve: c_int, num_vars: usize, num_inputs: usize,
                                 domain_size: usize, a_query: *const c_void, b_g1_query: *const c_void,
                                 b_g2_query: *const c_void, h_query: *const c_void, l_query: *const c_void,
@@ -318,6 +322,7 @@ extern "C" {
                                delta_g2: *const c_void, ic: *const c_void, n_ic: usize, public_inputs: *const c_void,
                                n_public: usize, proof_affine: *const c_void, flags: c_uint, accepted: *mut c_int) -> c_int;
     // batched verification on the GPU (BN254, BLS12-381): a prepared verifying key and one call per batch
+    // with DG16_F_DEVICE_PTRS: synchronous; ordered behind the work enqueued on channel 0's stream; outputs complete on return
     pub fn dg16_vk_create(ctx: *mut Dg16Ctx, curve: c_int, alpha_g1: *const c_void, beta_g2: *const c_void,
                           gamma_g2: *const c_void, delta_g2: *const c_void, ic: *const c_void, n_ic: usize,
                           flags: c_uint, out: *mut *mut Dg16Vk) -> c_int;

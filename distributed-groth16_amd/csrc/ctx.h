@@ -175,6 +175,20 @@ struct Call {
   hipStream_t s() const { return c.cur; }
 };
 
+// The one-time synchronous entry points without a `channel` argument (dg16_pk_create*, dg16_vk_create, the two setups)
+// read their device inputs with blocking copies on the NULL stream, which does not order itself behind the library's or
+// a caller's non-blocking streams: they wait here, before the first read, for the work enqueued on channel 0's CURRENT
+// stream (the library's own or the one installed with dg16_set_stream), as the header promises for them.
+inline void sync_channel0(dg16_ctx* ctx) {
+  hipStream_t s;
+  {
+    std::lock_guard<std::mutex> g(ctx->ch[0].mu);
+    s = ctx->ch[0].cur;
+  }
+  DG_HIP(hipSetDevice(ctx->device));
+  DG_HIP(hipStreamSynchronize(s));
+}
+
 inline int guard_channel(dg16_ctx* ctx, int channel) {
   if (!ctx) return DG16_ERR_BAD_ARG;
   if (channel < 0 || channel >= kChannels) {

@@ -54,6 +54,7 @@ int dg16_pk_create_shard(dg16_ctx* ctx, int curve, size_t num_vars, size_t num_i
     pk->d.nshards = n_shards;
     pk->d.h_cyclic = (flags & DG16_F_H_CYCLIC) != 0;
     bool dev = flags & DG16_F_DEVICE_PTRS;
+    if (dev) sync_channel0(ctx);   // pk_build copies the queries on the NULL stream: wait for their producers first
     if (curve == DG16_BN254)
       pk_build_bn254(ctx, pk->d, a_query, b_g1_query, b_g2_query, h_query, l_query, fixed_points, dev);
     else

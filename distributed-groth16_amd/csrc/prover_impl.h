@@ -761,6 +761,9 @@ static void pk_build(dg16_ctx* ctx, PkDev& d, const void* a_query, const void* b
   DG_HIP(hipMemcpy(fixed + 3 * p1, b1, p1, kind));            // b_g1_query[0]
   DG_HIP(hipMemcpy(fixed + 4 * p1, fx + 3 * p1, p2, kind));   // beta_g2
   DG_HIP(hipMemcpy(fixed + 4 * p1 + p2, b2, p2, kind));       // b_g2_query[0]
+  // a device-to-device hipMemcpy need not hold the host, and the caller may overwrite the queries as soon as this returns.
+  // Unconditional on purpose: with host pointers the copies above have blocked already and this costs nothing.
+  DG_HIP(hipDeviceSynchronize());
 }
 
 

@@ -73,6 +73,7 @@ int dg16_groth16_setup(dg16_ctx* ctx, int curve, size_t num_constraints, size_t 
                "need 1 <= num_inputs <= num_vars and num_constraints + num_inputs <= 2^log_m");
     const bool dev = flags & DG16_F_DEVICE_PTRS;
     Call k(ctx, 0);
+    if (dev) DG_HIP(hipStreamSynchronize(k.s()));   // behind the producers on channel 0's stream, before row_ptr[nc] is read
     SetupArgs s{};
     s.nc = nc; s.ni = ni; s.nv = nv; s.log_m = log_m;
     s.trapdoor = trapdoor;
@@ -169,6 +170,7 @@ int dg16_groth16_setup_srs(dg16_ctx* ctx, int curve, size_t num_constraints, siz
                "need 1 <= num_inputs <= num_vars and num_constraints + num_inputs <= 2^log_m");
     const bool dev = flags & DG16_F_DEVICE_PTRS;
     Call k(ctx, 0);
+    if (dev) DG_HIP(hipStreamSynchronize(k.s()));   // behind the producers on channel 0's stream, before row_ptr[nc] is read
     SrsSetupArgs s{};
     s.nc = nc; s.ni = ni; s.nv = nv; s.log_m = log_m;
     s.in_subgroup = flags & DG16_F_BASES_IN_SUBGROUP;

@@ -27,6 +27,7 @@ int dg16_vk_create(dg16_ctx* ctx, int curve, const void* alpha_g1, const void* b
     std::vector<uint8_t> host;
     const void* src[5] = {alpha_g1, beta_g2, gamma_g2, delta_g2, ic};
     if (flags & DG16_F_DEVICE_PTRS) {
+      sync_channel0(ctx);   // the blocking copies below run on the NULL stream: wait for the key's producers first
       const size_t bytes[5] = {g1b, g2b, g2b, g2b, n_ic * g1b};
       host.resize(g1b + 3 * g2b + n_ic * g1b);
       size_t off = 0;

@@ -38,6 +38,10 @@
  *   - The library owns device memory; the caller owns every buffer it passes and may free it on
  *     return (host-pointer calls are synchronous; device-pointer calls are stream-ordered on the
  *     channel's stream -- use dg16_sync or the stream you installed with dg16_set_stream).
+ *   - The one-time calls WITHOUT a `channel` argument that take device pointers -- dg16_pk_create, dg16_pk_create_shard,
+ *     dg16_vk_create, dg16_groth16_setup, dg16_groth16_setup_srs -- are synchronous; ordered behind the work enqueued on
+ *     channel 0's stream (the library's own, or the one installed with dg16_set_stream(ctx, 0, ..)); outputs complete on
+ *     return.  An input that another stream is still producing must be joined to channel 0's stream by the caller.
  */
 #ifndef DG16_H
 #define DG16_H
@@ -243,7 +247,8 @@ unsigned dg16_fixed_base_window_bits(size_t n);
  *   a_query, b_g1_query [num_vars] G1 | b_g2_query [num_vars] G2 | h_query [2^log_m] G1 |
  *   l_query [num_vars - num_inputs] G1 | fixed_points = alpha_g1 | beta_g1 | delta_g1 | beta_g2 | delta_g2 (the
  *   dg16_pk_create layout) | gamma_g2 (one G2) | gamma_abc_g1 [num_inputs] G1.
- * Synchronous in both forms (it owns temporary device memory); runs on channel 0.  A matrix entry whose column is
+ * Synchronous in both forms (it owns temporary device memory); runs on channel 0.  With DG16_F_DEVICE_PTRS: synchronous;
+ * ordered behind the work enqueued on channel 0's stream; outputs complete on return.  A matrix entry whose column is
  * not a wire, or a row_ptr that is not ordered, is DG16_ERR_BAD_ARG.
  * flags | DG16_F_QAP_LIBSNARK: the LibsnarkReduction key -- h_query[i] = (tau^i Z(tau) / delta) G1 for i < m - 1 and zero
  * bytes at i = m - 1; every other output is byte-equal to the call without the flag. */
@@ -291,7 +296,8 @@ typedef struct dg16_srs {          /* affine points, identity = zero bytes; devi
  * Coefficients 0, 1 and r - 1 cost no multiplication; the others go through dg16_points_mul's loops, in slices of the
  * size dg16_ctx_set_points_mul_slice sets (0: 2^17 terms).  A wire's terms are added by one lane, by a wave (from
  * wave_from terms) or, from msm_from terms on, by the library's MSM (dg16_setup_srs_limits reports the two thresholds).
- * Synchronous in both pointer forms; runs on channel 0.  A matrix entry whose column is not a wire, or a row_ptr that
+ * Synchronous in both pointer forms; runs on channel 0.  With DG16_F_DEVICE_PTRS: synchronous; ordered behind the work
+ * enqueued on channel 0's stream; outputs complete on return.  A matrix entry whose column is not a wire, or a row_ptr that
  * is not ordered, is DG16_ERR_BAD_ARG, as is a NULL srs or a NULL array in it; nothing is read out of range. */
 int dg16_groth16_setup_srs(dg16_ctx *ctx, int curve, size_t num_constraints, size_t num_inputs, size_t num_vars,
                            unsigned log_m, const uint32_t *a_row_ptr, const uint32_t *a_col, const void *a_coeff,
@@ -311,7 +317,9 @@ void dg16_setup_srs_limits(unsigned *wave_from, unsigned *msm_from);
  * num_vars - num_inputs, h_query has domain_size entries (CircomReduction::h_query_scalars,
  * ark-circom/src/circom/qap.rs:94-110).  fixed_points = alpha_g1 | beta_g1 | delta_g1 (G1 affine)
  * | beta_g2 | delta_g2 (G2 affine), contiguous.  The base-vector mapping follows
- * groth16/src/proving_key.rs:48-65.  flags: DG16_F_DEVICE_PTRS if every pointer is a device pointer. */
+ * groth16/src/proving_key.rs:48-65.  flags: DG16_F_DEVICE_PTRS if every pointer is a device pointer.
+ * dg16_pk_create and dg16_pk_create_shard with DG16_F_DEVICE_PTRS: synchronous; ordered behind the work enqueued on
+ * channel 0's stream; outputs complete on return (the key is resident and the queries may be freed or overwritten). */
 /* HBM budget, in bytes, of the window tables of ONE resident key (dg16_pk_create*: the five tables together) or ONE
  * base set (dg16_bases_upload) built on this context from now on; 0 (the default) = unlimited.  A full table has one
  * row T[w] = 2^(c w) P per c-bit window (BN254, 2^20 wires, c = 17: 6.0 GB per key; BLS12-381 at 2^24: 126 GB).  Under a
@@ -688,6 +696,7 @@ int dg16_groth16_verify(int curve, const void *alpha_g1, const void *beta_g2, co
  * subgroup-checked too -- and does the per-key work once: the Miller value of (alpha, beta) and the Miller-loop line
  * tables of gamma and delta.  The key's pointers are host pointers, or all device pointers with DG16_F_DEVICE_PTRS
  * (no other flag is accepted); the call is synchronous and the handle owns its device memory until dg16_vk_destroy.
+ * With DG16_F_DEVICE_PTRS: synchronous; ordered behind the work enqueued on channel 0's stream; outputs complete on return.
  * dg16_groth16_verify_batch: public_inputs = n_proofs x n_public scalars (row i belongs to proof i), proofs_affine =
  * n_proofs x (A | B | C), verdict = n_proofs bytes.  verdict[i] = 1 iff proof i passes every check and the equation
  * holds, else 0.  n_public + 1 != n_ic returns DG16_ERR_LENGTH_MISMATCH; n_proofs = 0 is DG16_OK.  Whatever is wrong
