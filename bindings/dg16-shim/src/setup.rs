@@ -114,6 +114,72 @@ pub struct Srs<E: Pairing> {
     pub g2: E::G2Affine,
 }
 
+/// The monomial powers a powers-of-tau ceremony publishes for a domain of size m = `tau_g2.len()` (a power of two):
+/// `tau_g1` holds 2m - 1 points, the other arrays m.  The caller vouches that every point is of order r.
+pub struct SrsPowers<E: Pairing> {
+    pub tau_g1: Vec<E::G1Affine>,
+    pub tau_g2: Vec<E::G2Affine>,
+    pub alpha_tau_g1: Vec<E::G1Affine>,
+    pub beta_tau_g1: Vec<E::G1Affine>,
+    pub beta_g2: E::G2Affine,
+}
+
+/// From ceremony output to the reference string `setup_from_srs` takes (`dg16_srs_prepare`; snarkjs' `powersoftau
+/// prepare phase2`): four inverse group FFTs of size m and the h basis of the chosen reduction (`libsnark` false:
+/// CircomReduction).
+pub fn srs_prepare<E, P1, P2>(powers: &SrsPowers<E>, libsnark: bool) -> Result<Srs<E>, Dg16Error>
+where
+    E: Pairing<G1Affine = Affine<P1>, G2Affine = Affine<P2>>,
+    P1: Dg16Config<ScalarField = E::ScalarField>,
+    P2: Dg16Config<ScalarField = E::ScalarField>,
+    P1::BaseField: FieldBytes,
+    P2::BaseField: FieldBytes,
+{
+    let m = powers.tau_g2.len();
+    if !m.is_power_of_two() || powers.tau_g1.len() != 2 * m - 1 || powers.alpha_tau_g1.len() != m
+        || powers.beta_tau_g1.len() != m
+    {
+        return Err(Dg16Error::Status(sys::DG16_ERR_BAD_ARG, "powers: tau_g1 holds 2m - 1 points, the others m = 2^k".into()));
+    }
+    let log_m = m.trailing_zeros();
+    let (t1, t2) = (pack_affine(&powers.tau_g1), pack_affine(&powers.tau_g2));
+    let (at, bt, b2) = (pack_affine(&powers.alpha_tau_g1), pack_affine(&powers.beta_tau_g1), pack_affine(&[powers.beta_g2]));
+    let raw_in = sys::Dg16SrsPowers {
+        tau_g1: t1.as_ptr().cast(),
+        tau_g2: t2.as_ptr().cast(),
+        alpha_tau_g1: at.as_ptr().cast(),
+        beta_tau_g1: bt.as_ptr().cast(),
+        beta_g2: b2.as_ptr().cast(),
+    };
+    let (f1, f2) = (2 * <P1::BaseField as FieldBytes>::BYTES, 2 * <P2::BaseField as FieldBytes>::BYTES);
+    let (mut l1, mut l2) = (vec![0u8; m * f1], vec![0u8; m * f2]);
+    let (mut al, mut bl, mut hb) = (vec![0u8; m * f1], vec![0u8; m * f1], vec![0u8; m * f1]);
+    let mut fixed = vec![0u8; 3 * f1 + 2 * f2];
+    let mut raw_out = sys::Dg16SrsPrepared {
+        lag_g1: l1.as_mut_ptr().cast(),
+        lag_g2: l2.as_mut_ptr().cast(),
+        alpha_lag_g1: al.as_mut_ptr().cast(),
+        beta_lag_g1: bl.as_mut_ptr().cast(),
+        h_g1: hb.as_mut_ptr().cast(),
+        fixed: fixed.as_mut_ptr().cast(),
+    };
+    check(unsafe { sys::dg16_srs_prepare(CTX.0, P1::CURVE, log_m, if libsnark { 1 } else { 0 }, &raw_in, &mut raw_out) })?;
+    let g1_fixed = unpack_affine::<P1>(&fixed[..3 * f1]);
+    let g2_fixed = unpack_affine::<P2>(&fixed[3 * f1..]);
+    Ok(Srs::<E> {
+        lag_g1: unpack_affine::<P1>(&l1),
+        lag_g2: unpack_affine::<P2>(&l2),
+        alpha_lag_g1: unpack_affine::<P1>(&al),
+        beta_lag_g1: unpack_affine::<P1>(&bl),
+        h_g1: unpack_affine::<P1>(&hb),
+        alpha_g1: g1_fixed[0],
+        beta_g1: g1_fixed[1],
+        g1: g1_fixed[2],
+        beta_g2: g2_fixed[0],
+        g2: g2_fixed[1],
+    })
+}
+
 /// The key of `m` computed in the exponent from `srs` (`dg16_groth16_setup_srs`): gamma = delta = 1, no trapdoor.
 /// `in_subgroup` passes DG16_F_BASES_IN_SUBGROUP (the endomorphism split of the coefficients).
 pub fn setup_from_srs<E, P1, P2>(m: &ConstraintMatrices<E::ScalarField>, srs: &Srs<E>, in_subgroup: bool)

@@ -142,6 +142,27 @@ pub struct Dg16Srs {
     pub h_g1: *const c_void,
     pub fixed: *const c_void,
 }
+/// `dg16_srs_powers`: the monomial powers of a ceremony, the input of `dg16_srs_prepare` (HOST pointers)
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct Dg16SrsPowers {
+    pub tau_g1: *const c_void,
+    pub tau_g2: *const c_void,
+    pub alpha_tau_g1: *const c_void,
+    pub beta_tau_g1: *const c_void,
+    pub beta_g2: *const c_void,
+}
+/// `dg16_srs_prepared`: the caller-allocated HOST buffers `dg16_srs_prepare` fills, laid out as the arrays of `dg16_srs`
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct Dg16SrsPrepared {
+    pub lag_g1: *mut c_void,
+    pub lag_g2: *mut c_void,
+    pub alpha_lag_g1: *mut c_void,
+    pub beta_lag_g1: *mut c_void,
+    pub h_g1: *mut c_void,
+    pub fixed: *mut c_void,
+}
 /// `dg16_arkkey_layout_t`
 #[repr(C)]
 #[derive(Clone, Copy, Debug, Default)]
@@ -226,6 +247,12 @@ extern "C" {
                     l_query: *mut c_void, fixed_points: *mut c_void, gamma_g2: *mut c_void,
                     gamma_abc_g1: *mut c_void, flags: c_uint) -> c_int;
     pub fn dg16_setup_srs_limits(wave_from: *mut c_uint, msm_from: *mut c_uint);
+    // the radix-2 transform over group elements and the preparation of a reference string from a ceremony's monomial
+    // powers; host pointers only, synchronous, channel 0
+    pub fn dg16_group_ntt(ctx: *mut Dg16Ctx, curve: c_int, group: c_int, points_affine: *mut c_void, log_n: c_uint,
+                          inverse: c_int) -> c_int;
+    pub fn dg16_srs_prepare(ctx: *mut Dg16Ctx, curve: c_int, log_m: c_uint, reduction: c_int,
+                            powers: *const Dg16SrsPowers, out: *mut Dg16SrsPrepared) -> c_int;
     pub fn dg16_to_affine(ctx: *mut Dg16Ctx, curve: c_int, group: c_int, jac: *const c_void, out: *mut c_void,
                           n: usize, flags: c_uint, channel: c_int) -> c_int;
     // resident bases (a CRS is uploaded once; msm over its window tables)

@@ -11,6 +11,11 @@ ceremony (`dg16_groth16_setup_srs`, csrc/setup_srs_curve.hip); it has gamma = de
 
     params = generate_parameters_from_srs(ctx, "bn254", r1cs, srs)      # srs: an Srs, e.g. decoded from a prepared .ptau
 
+and an Srs comes from the monomial powers a ceremony publishes through the group transform (`dg16_srs_prepare`,
+csrc/group_ntt_curve.hip; snarkjs' `powersoftau prepare phase2`):
+
+    srs = srs_from_powers(ctx, "bn254", log_m, tau_g1, tau_g2, alpha_tau_g1, beta_tau_g1, beta_g2)
+
 The trapdoor (alpha, beta, gamma, delta, tau) is drawn from `secrets` unless the caller passes one; it is returned with
 the parameters only when it was passed in.  torch is the device-memory plumbing; there is no CPU path."""
 
@@ -243,6 +248,42 @@ def srs_from_trapdoor(ctx, curve, log_m, alpha, beta, tau, reduction="circom"):
               ctx.fixed_base_mul(curve, 1, h), np.concatenate([ab.reshape(-1), b2.reshape(-1)]), reduction=reduction)
     srs.u, srs.h = u, h
     return srs
+
+
+def powers_from_trapdoor(ctx, curve, log_m, alpha, beta, tau):
+    """FOR TESTS AND BENCHMARKS ONLY, like srs_from_trapdoor: the monomial powers a ceremony with the KNOWN secrets alpha,
+    beta, tau would publish over the standard generators, as dg16_fixed_base_mul products of tau^j.
+    -> (tau_g1 [2m - 1], tau_g2 [m], alpha_tau_g1 [m], beta_tau_g1 [m], beta_g2 [1]), host arrays."""
+    r = FR_MODULUS[curve]
+    alpha, beta, tau = int(alpha), int(beta), int(tau)
+    if any(not 0 < x < r for x in (alpha, beta, tau)):
+        raise ValueError("alpha, beta, tau must be non-zero and below r")
+    if log_m + 1 > TWO_ADICITY[curve] or log_m > 26:
+        raise ValueError("domain larger than the field's 2-adic subgroup")
+    m = 1 << log_m
+    pw = [1] * (2 * m - 1)
+    for j in range(1, 2 * m - 1):
+        pw[j] = pw[j - 1] * tau % r
+    ab = ctx.fixed_base_mul(curve, 1, _ints_to_arr([alpha, beta]))
+    first = _ints_to_arr(pw[:m])
+    return (ctx.fixed_base_mul(curve, 1, _ints_to_arr(pw)), ctx.fixed_base_mul(curve, 2, first),
+            ctx.fixed_base_mul(curve, 1, first, base=ab[0]), ctx.fixed_base_mul(curve, 1, first, base=ab[1]),
+            ctx.fixed_base_mul(curve, 2, _ints_to_arr([beta])))
+
+
+def srs_from_powers(ctx, curve, log_m, tau_g1, tau_g2, alpha_tau_g1, beta_tau_g1, beta_g2, reduction="circom"):
+    """The reference string of the domain of size 2^log_m from a ceremony's monomial powers (`dg16_srs_prepare`): host
+    arrays tau_g1 [2m - 1] G1, tau_g2 [m] G2, alpha_tau_g1 and beta_tau_g1 [m] G1, beta_g2 one G2 point, in this
+    library's affine Montgomery layout.  reduction names the QAP reduction the h basis is made for; it is recorded on
+    the result.  The points must be on their curves and of order r: nothing here checks that.  Returns an Srs of host
+    arrays."""
+    _lib._reduction_flag(reduction)
+    if curve not in FR_MODULUS:
+        raise ValueError("unknown curve %r" % (curve,))
+    if log_m + 1 > TWO_ADICITY[curve] or log_m > 26:
+        raise ValueError("domain larger than the field's 2-adic subgroup")
+    out = ctx.srs_prepare(curve, log_m, tau_g1, tau_g2, alpha_tau_g1, beta_tau_g1, beta_g2, reduction=reduction)
+    return Srs(curve, log_m, *out, reduction=reduction)
 
 
 def generate_parameters_from_srs(ctx, curve, r1cs, srs, reduction="circom", in_subgroup=False):

@@ -57,6 +57,14 @@ class Srs(ctypes.Structure):              # dg16_srs
     _fields_ = [(n, ctypes.c_void_p) for n in ("lag_g1", "lag_g2", "alpha_lag_g1", "beta_lag_g1", "h_g1", "fixed")]
 
 
+class SrsPowers(ctypes.Structure):        # dg16_srs_powers
+    _fields_ = [(n, ctypes.c_void_p) for n in ("tau_g1", "tau_g2", "alpha_tau_g1", "beta_tau_g1", "beta_g2")]
+
+
+class SrsPrepared(ctypes.Structure):      # dg16_srs_prepared
+    _fields_ = [(n, ctypes.c_void_p) for n in ("lag_g1", "lag_g2", "alpha_lag_g1", "beta_lag_g1", "h_g1", "fixed")]
+
+
 class PkInfo(ctypes.Structure):           # dg16_pk_info
     _fields_ = [("n_ab", ctypes.c_uint64), ("n_l", ctypes.c_uint64), ("n_h", ctypes.c_uint64),
                 ("c_ab", ctypes.c_uint32), ("c_l", ctypes.c_uint32), ("c_h", ctypes.c_uint32),
@@ -261,6 +269,8 @@ def load():
     L.dg16_points_mul.argtypes = [vp, i, i, vp, vp, sz, vp, u, i]
     L.dg16_ctx_set_points_mul_slice.argtypes = [vp, sz]
     L.dg16_groth16_rerandomize.argtypes = [vp, vp, vp, sz, vp, u, vp, i]
+    L.dg16_group_ntt.argtypes = [vp, i, i, vp, u, i]
+    L.dg16_srs_prepare.argtypes = [vp, i, u, i, ctypes.POINTER(SrsPowers), ctypes.POINTER(SrsPrepared)]
     _lib = L
     return L
 
@@ -286,7 +296,7 @@ EXPORTED = ["dg16_ctx_create", "dg16_ctx_destroy", "dg16_last_error", "dg16_set_
             "dg16_ctx_set_table_budget", "dg16_fixed_base_mul", "dg16_fixed_base_window_bits", "dg16_groth16_setup",
             "dg16_vk_create", "dg16_vk_destroy", "dg16_groth16_verify_batch", "dg16_groth16_verify_aggregate",
             "dg16_points_mul", "dg16_ctx_set_points_mul_slice", "dg16_groth16_rerandomize",
-            "dg16_groth16_setup_srs", "dg16_setup_srs_limits"]
+            "dg16_groth16_setup_srs", "dg16_setup_srs_limits", "dg16_group_ntt", "dg16_srs_prepare"]
 
 
 def _ptr(x):
@@ -611,6 +621,43 @@ class Context:
         self._chk(self.L.dg16_groth16_setup_srs(self.h, CURVES[curve], num_constraints, num_inputs, num_vars, log_m,
                                                 *[_ptr(x) for x in mats], None if s is None else ctypes.byref(s),
                                                 *[_ptr(x) for x in outputs], flags))
+
+    def group_ntt(self, curve, group, points, inverse=False):
+        """The transform of `ntt` over group elements (`dg16_group_ntt`): 2^k affine points of `group` (identity = zeros),
+        natural order in and out; for points s_j G the result is ntt(s)_i G.  Every point must be in the order-r subgroup
+        (not checked).  Host arrays; returns a transformed copy.  Synchronous."""
+        nl = FQ_LIMBS64[curve] * 2 * (2 if group == 2 else 1)
+        points = np.array(points, dtype=np.uint64, copy=True).reshape(-1, nl)
+        n = points.shape[0]
+        log_n = n.bit_length() - 1
+        if n == 0 or (1 << log_n) != n:
+            raise ValueError("transform size must be a power of two")
+        self._chk(self.L.dg16_group_ntt(self.h, CURVES[curve], group, _ptr(points), log_n, int(inverse)))
+        return points
+
+    def srs_prepare(self, curve, log_m, tau_g1, tau_g2, alpha_tau_g1, beta_tau_g1, beta_g2, reduction="circom"):
+        """`dg16_srs_prepare`: the monomial powers of a ceremony (host arrays: tau_g1 [2m - 1] G1, tau_g2 [m] G2,
+        alpha_tau_g1, beta_tau_g1 [m] G1, beta_g2 one G2 point; m = 2^log_m) -> (lag_g1, lag_g2, alpha_lag_g1,
+        beta_lag_g1, h_g1, fixed), the arrays `groth16_setup_srs` takes, h_g1 for the named reduction.  The points must
+        have order r (not checked).  Synchronous."""
+        if reduction not in ("circom", "libsnark"):
+            raise ValueError("reduction must be 'circom' or 'libsnark'")
+        fq = FQ_LIMBS64[curve]
+        m = 1 << log_m
+        want = ((2 * m - 1, 2 * fq), (m, 4 * fq), (m, 2 * fq), (m, 2 * fq), (1, 4 * fq))
+        ins = []
+        for name, arr, (rows, cols) in zip(SrsPowers._fields_, (tau_g1, tau_g2, alpha_tau_g1, beta_tau_g1, beta_g2), want):
+            arr = np.ascontiguousarray(arr, dtype=np.uint64)
+            if arr.size != rows * cols:
+                raise ValueError("%s must hold %d points" % (name[0], rows))
+            ins.append(arr.reshape(rows, cols))
+        outs = [np.zeros((m, c), dtype=np.uint64) for c in (2 * fq, 4 * fq, 2 * fq, 2 * fq, 2 * fq)]
+        outs.append(np.zeros(3 * 2 * fq + 2 * 4 * fq, dtype=np.uint64))
+        pw = SrsPowers(*[a.ctypes.data for a in ins])
+        pr = SrsPrepared(*[a.ctypes.data for a in outs])
+        self._chk(self.L.dg16_srs_prepare(self.h, CURVES[curve], log_m, 1 if reduction == "libsnark" else 0,
+                                          ctypes.byref(pw), ctypes.byref(pr)))
+        return tuple(outs)
 
     def to_affine(self, curve, group, jac, channel=0):
         jac = np.ascontiguousarray(jac, dtype=np.uint64)

@@ -270,8 +270,8 @@ int dg16_groth16_setup(dg16_ctx *ctx, int curve, size_t num_constraints, size_t 
  *   h_g1   the h basis of the QAP reduction the key will be proved with, for delta = 1.  CircomReduction: the points
  *       L'_{2i+1}(tau) G of the size-2m Lagrange basis with odd index (snarkjs reads them from the block of the power
  *       log_m + 1 of section 12), i < m.  LibsnarkReduction: tau^i Z(tau) G = (tau^(i+m) - tau^i) G for i < m - 1
- *       and the identity at i = m - 1.  It is copied to h_query as it stands: deriving it from tau powers needs a
- *       group NTT, which is not part of this call.
+ *       and the identity at i = m - 1.  It is copied to h_query as it stands; dg16_srs_prepare derives it, and the
+ *       four arrays above, from the tau powers a ceremony publishes.
  *   fixed  alpha G1, beta G1, G1, beta G2, G2: the first elements of sections 4 (alphaTauG1), 5 (betaTauG1) and 2
  *       (tauG1), section 6 (betaG2) and the first element of section 3 (tauG2).
  * THE CALLER GUARANTEES that every point of the reference string is on its curve and in the subgroup of order r --
@@ -306,6 +306,52 @@ int dg16_groth16_setup_srs(dg16_ctx *ctx, int curve, size_t num_constraints, siz
                            const dg16_srs *srs, void *a_query, void *b_g1_query, void *b_g2_query, void *h_query,
                            void *l_query, void *fixed_points, void *gamma_g2, void *gamma_abc_g1, unsigned flags);
 void dg16_setup_srs_limits(unsigned *wave_from, unsigned *msm_from);
+
+/* ---- group transform and reference-string preparation ------------------------------------------------------------
+ * The radix-2 transform of dg16_ntt over GROUP elements, in place on 2^log_n affine points of `group` (1 = G1, 2 = G2;
+ * identity = zero bytes), natural order in and out -- Radix2EvaluationDomain::{fft, ifft} on a Vec<G>:
+ *   forward  out[i] = sum_j w^(i j) P_j          inverse  out[i] = n^-1 sum_j w^(-i j) P_j
+ * with w the root dg16_ntt uses for the same curve and size: for P_j = s_j G the result is dg16_ntt(s)_i G.
+ * THE CALLER GUARANTEES that every point is in the subgroup of order r (a ceremony verifier checks that; this call
+ * does not).  The scalar field does not act on other points: for them the result is unspecified, but nothing is read or
+ * written out of range.  Every stage is n / 2 butterflies (a, b) -> (a + w b, a - w b), one lane each, cut into slices
+ * of the size dg16_ctx_set_points_mul_slice sets; the butterflies with w = 1 (all of the first stage, n / 2^s of stage
+ * s) add and subtract only, so a forward transform costs (n / 2) log_n - (n - 1) point multiplications and an inverse
+ * n more.  points_affine: host pointers only.  Synchronous; runs on channel 0; the device copies are temporary
+ * (DG16_ERR_OOM leaves the context usable).  log_n <= min(two-adicity of r, 27), else DG16_ERR_BAD_ARG; log_n = 0 is a
+ * no-op. */
+int dg16_group_ntt(dg16_ctx *ctx, int curve, int group, void *points_affine, unsigned log_n, int inverse);
+
+/* The monomial powers a powers-of-tau ceremony publishes (the sections of a .ptau file, decoded to this library's affine
+ * Montgomery layout), m = 2^log_m.  All five are host pointers. */
+typedef struct dg16_srs_powers {
+  const void *tau_g1;              /* [2m - 1] tau^j G1          (section 2) */
+  const void *tau_g2;              /* [m]      tau^j G2          (section 3) */
+  const void *alpha_tau_g1;        /* [m]      alpha tau^j G1    (section 4) */
+  const void *beta_tau_g1;         /* [m]      beta tau^j G1     (section 5) */
+  const void *beta_g2;             /* one G2 point: beta G2      (section 6) */
+} dg16_srs_powers;
+/* What dg16_srs_prepare writes: caller-allocated host buffers, laid out as the arrays of dg16_srs. */
+typedef struct dg16_srs_prepared {
+  void *lag_g1;                    /* [m] G1 */
+  void *lag_g2;                    /* [m] G2 */
+  void *alpha_lag_g1;              /* [m] G1 */
+  void *beta_lag_g1;               /* [m] G1 */
+  void *h_g1;                      /* [m] G1 */
+  void *fixed;                     /* alpha_g1 | beta_g1 | g1 (G1 affine) | beta_g2 | g2 (G2 affine) */
+} dg16_srs_prepared;
+
+/* From ceremony output to the reference string dg16_groth16_setup_srs takes (snarkjs `powersoftau prepare phase2`):
+ *   lag_g1, lag_g2, alpha_lag_g1, beta_lag_g1   the inverse dg16_group_ntt of size m of the first m powers
+ *   h_g1, reduction 0 (CircomReduction)    the odd-indexed outputs of the inverse transform of size 2m of
+ *                                          tau_g1[0 .. 2m - 1) | identity
+ *   h_g1, reduction 1 (LibsnarkReduction)  tau_g1[i + m] - tau_g1[i] for i < m - 1, the identity at m - 1
+ *   fixed   alpha_tau_g1[0] | beta_tau_g1[0] | tau_g1[0] | beta_g2 | tau_g2[0]
+ * The caller's guarantee is dg16_group_ntt's: every point has order r.  powers, out and every array in them: host
+ * pointers only.  Synchronous; runs on channel 0.  log_m + 1 <= two-adicity of r and log_m <= 26, else
+ * DG16_ERR_BAD_ARG, as are a NULL pointer and another reduction; an unknown curve is DG16_ERR_BAD_CURVE. */
+int dg16_srs_prepare(dg16_ctx *ctx, int curve, unsigned log_m, int reduction, const dg16_srs_powers *powers,
+                     dg16_srs_prepared *out);
 
 /* ---- Groth16 prover (single prover; the value the n-party run must equal) ------------------------
  * Replaces `Groth16::<E, CircomReduction>::create_proof_with_reduction_and_matrices` (third-party
