@@ -180,6 +180,58 @@ where
     })
 }
 
+/// Curve and subgroup membership of affine points (`dg16_points_check`): `(bad points, smallest bad index)`, the index
+/// being `points.len()` when there is none.  A point is bad when a coordinate is not reduced, when it is off its curve
+/// or -- with `subgroup` -- when it is outside the subgroup of order r.  The identity is good.
+pub fn points_check<P>(points: &[Affine<P>], subgroup: bool) -> Result<(usize, usize), Dg16Error>
+where
+    P: Dg16Config,
+    P::BaseField: FieldBytes,
+{
+    let raw = pack_affine(points);
+    let (mut n_bad, mut first_bad) = (0usize, 0usize);
+    check(unsafe {
+        sys::dg16_points_check(CTX.0, P::CURVE, P::GROUP, raw.as_ptr().cast(), points.len(), if subgroup { 1 } else { 0 },
+                               &mut n_bad, &mut first_bad)
+    })?;
+    Ok((n_bad, first_bad))
+}
+
+/// Is this a powers-of-tau transcript (`dg16_srs_verify`)?  `coeffs`: 2m - 2 integers in [1, 2^128), independent,
+/// uniform and drawn AFTER the transcript was fixed -- the caller's randomness, as for the aggregate verifier.
+/// `report.failed == 0` accepts; its bits are `sys::DG16_SRS_*`.  A rejected transcript is `Ok` with the bits set; a
+/// zero coefficient is an error.  `srs_prepare` trusts its input: verify first.
+pub fn srs_verify<E, P1, P2>(powers: &SrsPowers<E>, coeffs: &[u128]) -> Result<sys::Dg16SrsReport, Dg16Error>
+where
+    E: Pairing<G1Affine = Affine<P1>, G2Affine = Affine<P2>>,
+    P1: Dg16Config<ScalarField = E::ScalarField>,
+    P2: Dg16Config<ScalarField = E::ScalarField>,
+    P1::BaseField: FieldBytes,
+    P2::BaseField: FieldBytes,
+{
+    let m = powers.tau_g2.len();
+    if !m.is_power_of_two() || m < 2 || powers.tau_g1.len() != 2 * m - 1 || powers.alpha_tau_g1.len() != m
+        || powers.beta_tau_g1.len() != m || coeffs.len() != 2 * m - 2
+    {
+        return Err(Dg16Error::Status(sys::DG16_ERR_BAD_ARG,
+                                     "powers: tau_g1 holds 2m - 1 points, the others m = 2^k >= 2; 2m - 2 coefficients".into()));
+    }
+    let log_m = m.trailing_zeros();
+    let (t1, t2) = (pack_affine(&powers.tau_g1), pack_affine(&powers.tau_g2));
+    let (at, bt, b2) = (pack_affine(&powers.alpha_tau_g1), pack_affine(&powers.beta_tau_g1), pack_affine(&[powers.beta_g2]));
+    let raw_in = sys::Dg16SrsPowers {
+        tau_g1: t1.as_ptr().cast(),
+        tau_g2: t2.as_ptr().cast(),
+        alpha_tau_g1: at.as_ptr().cast(),
+        beta_tau_g1: bt.as_ptr().cast(),
+        beta_g2: b2.as_ptr().cast(),
+    };
+    let rho: Vec<u8> = coeffs.iter().flat_map(|c| c.to_le_bytes()).collect();
+    let mut report = sys::Dg16SrsReport::default();
+    check(unsafe { sys::dg16_srs_verify(CTX.0, P1::CURVE, log_m, &raw_in, rho.as_ptr().cast(), &mut report) })?;
+    Ok(report)
+}
+
 /// The key of `m` computed in the exponent from `srs` (`dg16_groth16_setup_srs`): gamma = delta = 1, no trapdoor.
 /// `in_subgroup` passes DG16_F_BASES_IN_SUBGROUP (the endomorphism split of the coefficients).
 pub fn setup_from_srs<E, P1, P2>(m: &ConstraintMatrices<E::ScalarField>, srs: &Srs<E>, in_subgroup: bool)

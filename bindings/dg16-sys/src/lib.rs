@@ -152,6 +152,22 @@ pub struct Dg16SrsPowers {
     pub beta_tau_g1: *const c_void,
     pub beta_g2: *const c_void,
 }
+/// `dg16_srs_report`: what `dg16_srs_verify` found (failed = 0: accepted; the DG16_SRS_* bits below)
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default, PartialEq, Eq)]
+pub struct Dg16SrsReport {
+    pub failed: u32,
+    pub bad_array: u32,
+    pub bad_index: u64,
+    pub n_bad_points: u64,
+}
+pub const DG16_SRS_BAD_POINT: u32 = 1;
+pub const DG16_SRS_IDENTITY: u32 = 2;
+pub const DG16_SRS_TAU_G1: u32 = 4;
+pub const DG16_SRS_TAU_G2: u32 = 8;
+pub const DG16_SRS_ALPHA: u32 = 16;
+pub const DG16_SRS_BETA: u32 = 32;
+pub const DG16_SRS_BETA_G2: u32 = 64;
 /// `dg16_srs_prepared`: the caller-allocated HOST buffers `dg16_srs_prepare` fills, laid out as the arrays of `dg16_srs`
 #[repr(C)]
 #[derive(Clone, Copy, Debug)]
@@ -253,6 +269,12 @@ extern "C" {
                           inverse: c_int) -> c_int;
     pub fn dg16_srs_prepare(ctx: *mut Dg16Ctx, curve: c_int, log_m: c_uint, reduction: c_int,
                             powers: *const Dg16SrsPowers, out: *mut Dg16SrsPrepared) -> c_int;
+    // curve and subgroup membership of affine points, and the checks of a powers-of-tau transcript under the caller's
+    // 128-bit coefficients; host pointers only, synchronous, channel 0.  Bad points / a bad transcript are results.
+    pub fn dg16_points_check(ctx: *mut Dg16Ctx, curve: c_int, group: c_int, points_affine: *const c_void, n: usize,
+                             subgroup: c_int, n_bad: *mut usize, first_bad: *mut usize) -> c_int;
+    pub fn dg16_srs_verify(ctx: *mut Dg16Ctx, curve: c_int, log_m: c_uint, powers: *const Dg16SrsPowers,
+                           coeffs: *const c_void, report: *mut Dg16SrsReport) -> c_int;
     pub fn dg16_to_affine(ctx: *mut Dg16Ctx, curve: c_int, group: c_int, jac: *const c_void, out: *mut c_void,
                           n: usize, flags: c_uint, channel: c_int) -> c_int;
     // resident bases (a CRS is uploaded once; msm over its window tables)

@@ -20,4 +20,5 @@ from .lib import (  # noqa: F401
 from .keygen import generate_parameters, Parameters  # noqa: F401,E402
 from .keygen import generate_parameters_from_srs, srs_from_trapdoor, Srs  # noqa: F401,E402
 from .keygen import srs_from_powers, powers_from_trapdoor  # noqa: F401,E402
+from .keygen import verify_powers, SrsReport  # noqa: F401,E402
 from .verify import PreparedVerifyingKey  # noqa: F401,E402

@@ -1,0 +1,98 @@
+// C ABI of the membership check and of the transcript verifier (include/dg16.h): dg16_points_check, dg16_srs_verify.
+// Argument checks, the device copies of the host arrays and the dispatch on the curve; the kernel and the transcript
+// checks live in the per-curve objects (points_check_curve.hip).  Both calls take host pointers only, run on channel 0
+// and are synchronous; their device buffers are freed on every path.
+#include "points_check.h"
+
+using namespace dg16;
+
+namespace {
+
+constexpr unsigned kTwoAdicity[3] = {28, 32, 47};
+
+struct DeviceBuffer {
+  void* p = nullptr;
+  explicit DeviceBuffer(size_t bytes) { DG_HIP(hipMalloc(&p, bytes ? bytes : 16)); }
+  ~DeviceBuffer() {      // (hipFree waits for the kernels that still use the buffer)
+    if (p) (void)hipFree(p);
+  }
+  DeviceBuffer(const DeviceBuffer&) = delete;
+  DeviceBuffer& operator=(const DeviceBuffer&) = delete;
+};
+
+void check(Call& k, int curve, int group, const void* dev, size_t n, size_t index0, int subgroup,
+           pchk::CheckResult* res) {
+  switch (curve) {
+    case 0: points_check_run<0>(k, group, dev, n, index0, subgroup, res); break;
+    case 1: points_check_run<1>(k, group, dev, n, index0, subgroup, res); break;
+    default: points_check_run<2>(k, group, dev, n, index0, subgroup, res); break;
+  }
+}
+
+}  // namespace
+
+extern "C" {
+
+int dg16_points_check(dg16_ctx* ctx, int curve, int group, const void* points_affine, size_t n, int subgroup,
+                      size_t* n_bad, size_t* first_bad) {
+  if (!ctx) return DG16_ERR_BAD_ARG;
+  return guarded(ctx, [&] {
+    DG_REQUIRE(curve >= 0 && curve <= 2, DG16_ERR_BAD_CURVE, "unknown curve id");
+    DG_REQUIRE(group == 1 || group == 2, DG16_ERR_BAD_ARG, "group must be 1 (G1) or 2 (G2)");
+    DG_REQUIRE(n_bad && first_bad && (n == 0 || points_affine), DG16_ERR_BAD_ARG, "null argument");
+    DG_REQUIRE(n < ((size_t)1 << 30), DG16_ERR_BAD_ARG, "n must be < 2^30");
+    *n_bad = 0;
+    *first_bad = n;
+    if (!n) return;
+    size_t slice = ctx->points_mul_slice ? ctx->points_mul_slice : pchk::kSliceDefault;
+    slice = (slice + 63) / 64 * 64;
+    if (slice > n) slice = n;
+    const size_t pb = affine_bytes(curve, group);
+    Call k(ctx, 0);
+    DeviceBuffer pts(slice * pb), dres(sizeof(pchk::CheckResult));
+    pchk::CheckResult res = {0ull, (unsigned long long)n};
+    DG_HIP(hipMemcpyAsync(dres.p, &res, sizeof res, hipMemcpyHostToDevice, k.s()));
+    k.begin_dominant();
+    for (size_t lo = 0; lo < n; lo += slice) {
+      const size_t cnt = n - lo < slice ? n - lo : slice;
+      // (the copy is ordered behind the previous slice's kernel on the stream)
+      DG_HIP(hipMemcpyAsync(pts.p, (const char*)points_affine + lo * pb, cnt * pb, hipMemcpyHostToDevice, k.s()));
+      check(k, curve, group, pts.p, cnt, lo, subgroup != 0, (pchk::CheckResult*)dres.p);
+    }
+    k.end_dominant();
+    DG_HIP(hipMemcpyAsync(&res, dres.p, sizeof res, hipMemcpyDeviceToHost, k.s()));
+    k.finish();
+    DG_HIP(hipStreamSynchronize(k.s()));
+    *n_bad = (size_t)res.n_bad;
+    *first_bad = (size_t)res.first_bad;
+  });
+}
+
+int dg16_srs_verify(dg16_ctx* ctx, int curve, unsigned log_m, const dg16_srs_powers* powers, const void* coeffs,
+                    dg16_srs_report* report) {
+  if (!ctx) return DG16_ERR_BAD_ARG;
+  return guarded(ctx, [&] {
+    DG_REQUIRE(curve >= 0 && curve <= 2, DG16_ERR_BAD_CURVE, "unknown curve id");
+    DG_REQUIRE(curve != DG16_BLS12_377, DG16_ERR_UNSUPPORTED, "transcript verification: BN254 and BLS12-381 only");
+    DG_REQUIRE(powers && powers->tau_g1 && powers->tau_g2 && powers->alpha_tau_g1 && powers->beta_tau_g1 &&
+                   powers->beta_g2,
+               DG16_ERR_BAD_ARG, "null powers");
+    DG_REQUIRE(coeffs && report, DG16_ERR_BAD_ARG, "null argument");
+    DG_REQUIRE(log_m >= 1 && log_m <= pchk::kMaxLogM && log_m + 1 <= kTwoAdicity[curve], DG16_ERR_BAD_ARG,
+               "need 1 <= log_m <= 26 and a domain of 2m inside the field's 2-adic subgroup");
+    const pchk::SrsShape sh = pchk::srs_shape(log_m);
+    const uint8_t* c = (const uint8_t*)coeffs;
+    for (size_t j = 0; j < sh.n_long; j++) {
+      uint8_t any = 0;
+      for (int b = 0; b < 16; b++) any |= c[16 * j + b];
+      DG_REQUIRE(any, DG16_ERR_BAD_ARG, "a coefficient is zero");
+    }
+    Call k(ctx, 0);
+    if (curve == DG16_BN254) srs_verify_run<0>(k, log_m, powers, coeffs, report);
+    else srs_verify_run<1>(k, log_m, powers, coeffs, report);
+    k.finish();
+    DG_HIP(hipStreamSynchronize(k.s()));
+  });
+}
+
+}  // extern "C"

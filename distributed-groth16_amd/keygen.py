@@ -286,6 +286,63 @@ def srs_from_powers(ctx, curve, log_m, tau_g1, tau_g2, alpha_tau_g1, beta_tau_g1
     return Srs(curve, log_m, *out, reduction=reduction)
 
 
+class SrsReport:
+    """What `verify_powers` found: `.accepted`, the word `.failed` (0 = accepted) and a name per bit of it, the bits of
+    dg16_srs_report in include/dg16.h.  With BAD_POINT: `.bad_array` (the name of the first array that holds a bad point),
+    `.bad_index` (the smallest bad index in it) and `.n_bad_points` (over all five arrays).  `.generators_match` is None
+    unless `verify_powers` was given generators to compare with."""
+
+    BAD_POINT, IDENTITY, TAU_G1, TAU_G2, ALPHA, BETA, BETA_G2 = 1, 2, 4, 8, 16, 32, 64
+    NAMES = {1: "bad_point", 2: "identity", 4: "tau_g1", 8: "tau_g2", 16: "alpha", 32: "beta", 64: "beta_g2"}
+    ARRAYS = ("tau_g1", "tau_g2", "alpha_tau_g1", "beta_tau_g1", "beta_g2")
+
+    def __init__(self, failed, bad_array=0, bad_index=0, n_bad_points=0, generators_match=None):
+        self.failed = int(failed)
+        self.n_bad_points = int(n_bad_points)
+        self.bad_array = self.ARRAYS[bad_array] if self.failed & self.BAD_POINT else None
+        self.bad_index = int(bad_index) if self.failed & self.BAD_POINT else None
+        self.generators_match = generators_match
+        for bit, name in self.NAMES.items():
+            setattr(self, name, bool(self.failed & bit))
+
+    @property
+    def accepted(self):
+        return self.failed == 0 and self.generators_match is not False
+
+    @property
+    def reasons(self):
+        return [name for bit, name in self.NAMES.items() if self.failed & bit]
+
+    def __repr__(self):
+        return "SrsReport(accepted=%r, failed=%d %r)" % (self.accepted, self.failed, self.reasons)
+
+
+def verify_powers(ctx, curve, log_m, tau_g1, tau_g2, alpha_tau_g1, beta_tau_g1, beta_g2, coeffs=None, generators=None):
+    """Is this the output of a powers-of-tau ceremony (`dg16_srs_verify`; snarkjs' `powersoftau verify` without the
+    contribution chain)?  The arrays are those of `srs_from_powers`, which trusts them: verify first.  Every point must
+    be reduced, on its curve and of order r; the seven head points must not be the identity; and tau_g1, tau_g2,
+    alpha_tau_g1, beta_tau_g1 must be geometric progressions in one tau, beta_g2 holding beta_tau_g1's beta -- each
+    decided by one pairing equation on a random linear combination.  coeffs: uint64 [2m - 2][2], independent and uniform
+    in [1, 2^128) and drawn AFTER the transcript was fixed; None draws them with `verify.random_coefficients`.  A
+    transcript that fails an equation is then accepted with probability about 2^-128.  generators = (g1, g2) packed
+    affine points: tau_g1[0] and tau_g2[0] are also compared with them (a byte comparison), and a difference makes
+    `.accepted` False.  BN254 and BLS12-381.  Returns an SrsReport."""
+    if curve not in FR_MODULUS:
+        raise ValueError("unknown curve %r" % (curve,))
+    if coeffs is None:
+        from .verify import random_coefficients
+        coeffs = random_coefficients(2 * (1 << log_m) - 2)
+    rep = ctx.srs_verify(curve, log_m, tau_g1, tau_g2, alpha_tau_g1, beta_tau_g1, beta_g2, coeffs)
+    match = None
+    if generators is not None:
+        g1 = np.ascontiguousarray(generators[0], dtype=np.uint64).reshape(-1)
+        g2 = np.ascontiguousarray(generators[1], dtype=np.uint64).reshape(-1)
+        t = np.ascontiguousarray(tau_g1, dtype=np.uint64).reshape(-1)
+        u = np.ascontiguousarray(tau_g2, dtype=np.uint64).reshape(-1)
+        match = bool(np.array_equal(t[:g1.size], g1) and np.array_equal(u[:g2.size], g2))
+    return SrsReport(*rep, generators_match=match)
+
+
 def generate_parameters_from_srs(ctx, curve, r1cs, srs, reduction="circom", in_subgroup=False):
     """The key of `r1cs` from a structured reference string (an Srs for the domain of the system: log_m must match), in
     the exponent: gamma = delta = 1 and no trapdoor anywhere.  reduction names the QAP reduction srs.h_g1 was made for

@@ -65,6 +65,11 @@ class SrsPrepared(ctypes.Structure):      # dg16_srs_prepared
     _fields_ = [(n, ctypes.c_void_p) for n in ("lag_g1", "lag_g2", "alpha_lag_g1", "beta_lag_g1", "h_g1", "fixed")]
 
 
+class SrsReportC(ctypes.Structure):       # dg16_srs_report
+    _fields_ = [("failed", ctypes.c_uint32), ("bad_array", ctypes.c_uint32), ("bad_index", ctypes.c_uint64),
+                ("n_bad_points", ctypes.c_uint64)]
+
+
 class PkInfo(ctypes.Structure):           # dg16_pk_info
     _fields_ = [("n_ab", ctypes.c_uint64), ("n_l", ctypes.c_uint64), ("n_h", ctypes.c_uint64),
                 ("c_ab", ctypes.c_uint32), ("c_l", ctypes.c_uint32), ("c_h", ctypes.c_uint32),
@@ -271,6 +276,8 @@ def load():
     L.dg16_groth16_rerandomize.argtypes = [vp, vp, vp, sz, vp, u, vp, i]
     L.dg16_group_ntt.argtypes = [vp, i, i, vp, u, i]
     L.dg16_srs_prepare.argtypes = [vp, i, u, i, ctypes.POINTER(SrsPowers), ctypes.POINTER(SrsPrepared)]
+    L.dg16_points_check.argtypes = [vp, i, i, vp, sz, i, ctypes.POINTER(sz), ctypes.POINTER(sz)]
+    L.dg16_srs_verify.argtypes = [vp, i, u, ctypes.POINTER(SrsPowers), vp, ctypes.POINTER(SrsReportC)]
     _lib = L
     return L
 
@@ -296,7 +303,8 @@ EXPORTED = ["dg16_ctx_create", "dg16_ctx_destroy", "dg16_last_error", "dg16_set_
             "dg16_ctx_set_table_budget", "dg16_fixed_base_mul", "dg16_fixed_base_window_bits", "dg16_groth16_setup",
             "dg16_vk_create", "dg16_vk_destroy", "dg16_groth16_verify_batch", "dg16_groth16_verify_aggregate",
             "dg16_points_mul", "dg16_ctx_set_points_mul_slice", "dg16_groth16_rerandomize",
-            "dg16_groth16_setup_srs", "dg16_setup_srs_limits", "dg16_group_ntt", "dg16_srs_prepare"]
+            "dg16_groth16_setup_srs", "dg16_setup_srs_limits", "dg16_group_ntt", "dg16_srs_prepare",
+            "dg16_points_check", "dg16_srs_verify"]
 
 
 def _ptr(x):
@@ -658,6 +666,39 @@ class Context:
         self._chk(self.L.dg16_srs_prepare(self.h, CURVES[curve], log_m, 1 if reduction == "libsnark" else 0,
                                           ctypes.byref(pw), ctypes.byref(pr)))
         return tuple(outs)
+
+    def points_check(self, curve, group, points, subgroup=True):
+        """`dg16_points_check`: are the affine points (host array, identity = zeros) reduced, on the curve or twist of
+        `group` and -- with subgroup=True -- of order r?  Returns (n_bad, first_bad), first_bad = n when there is no bad
+        point.  Bad points are a result, not an error.  Synchronous."""
+        nl = FQ_LIMBS64[curve] * 2 * (2 if group == 2 else 1)
+        points = np.ascontiguousarray(points, dtype=np.uint64).reshape(-1, nl)
+        n_bad, first = ctypes.c_size_t(0), ctypes.c_size_t(0)
+        self._chk(self.L.dg16_points_check(self.h, CURVES[curve], group, _ptr(points) if points.shape[0] else None,
+                                           points.shape[0], int(bool(subgroup)), ctypes.byref(n_bad), ctypes.byref(first)))
+        return n_bad.value, first.value
+
+    def srs_verify(self, curve, log_m, tau_g1, tau_g2, alpha_tau_g1, beta_tau_g1, beta_g2, coeffs):
+        """`dg16_srs_verify`: is this a powers-of-tau transcript?  The five arrays are those of `srs_prepare`; coeffs:
+        uint64 [2m - 2][2], little-endian 128-bit integers in [1, 2^128) -- independent, uniform and drawn AFTER the
+        transcript was fixed (`verify.random_coefficients`).  Returns (failed, bad_array, bad_index, n_bad_points);
+        failed = 0 accepts, its bits are the DG16_SRS_* of the header (`keygen.SrsReport` names them).  Synchronous."""
+        fq = FQ_LIMBS64[curve]
+        m = 1 << log_m
+        want = ((2 * m - 1, 2 * fq), (m, 4 * fq), (m, 2 * fq), (m, 2 * fq), (1, 4 * fq))
+        ins = []
+        for name, arr, (rows, cols) in zip(SrsPowers._fields_, (tau_g1, tau_g2, alpha_tau_g1, beta_tau_g1, beta_g2), want):
+            arr = np.ascontiguousarray(arr, dtype=np.uint64)
+            if arr.size != rows * cols:
+                raise ValueError("%s must hold %d points" % (name[0], rows))
+            ins.append(arr.reshape(rows, cols))
+        coeffs = np.ascontiguousarray(coeffs, dtype=np.uint64)
+        if coeffs.size != (2 * m - 2) * 2:
+            raise ValueError("coeffs must hold %d 128-bit integers" % (2 * m - 2))
+        pw = SrsPowers(*[a.ctypes.data for a in ins])
+        rep = SrsReportC()
+        self._chk(self.L.dg16_srs_verify(self.h, CURVES[curve], log_m, ctypes.byref(pw), _ptr(coeffs), ctypes.byref(rep)))
+        return rep.failed, rep.bad_array, rep.bad_index, rep.n_bad_points
 
     def to_affine(self, curve, group, jac, channel=0):
         jac = np.ascontiguousarray(jac, dtype=np.uint64)

@@ -313,8 +313,9 @@ void dg16_setup_srs_limits(unsigned *wave_from, unsigned *msm_from);
  *   forward  out[i] = sum_j w^(i j) P_j          inverse  out[i] = n^-1 sum_j w^(-i j) P_j
  * with w the root dg16_ntt uses for the same curve and size: for P_j = s_j G the result is dg16_ntt(s)_i G.
  * THE CALLER GUARANTEES that every point is in the subgroup of order r (a ceremony verifier checks that; this call
- * does not).  The scalar field does not act on other points: for them the result is unspecified, but nothing is read or
- * written out of range.  Every stage is n / 2 butterflies (a, b) -> (a + w b, a - w b), one lane each, cut into slices
+ * does not) (`dg16_srs_verify` checks it).  The scalar field does not act on other points: for them the result is
+ * unspecified, but nothing is read or written out of range.
+ * Every stage is n / 2 butterflies (a, b) -> (a + w b, a - w b), one lane each, cut into slices
  * of the size dg16_ctx_set_points_mul_slice sets; the butterflies with w = 1 (all of the first stage, n / 2^s of stage
  * s) add and subtract only, so a forward transform costs (n / 2) log_n - (n - 1) point multiplications and an inverse
  * n more.  points_affine: host pointers only.  Synchronous; runs on channel 0; the device copies are temporary
@@ -347,11 +348,69 @@ typedef struct dg16_srs_prepared {
  *                                          tau_g1[0 .. 2m - 1) | identity
  *   h_g1, reduction 1 (LibsnarkReduction)  tau_g1[i + m] - tau_g1[i] for i < m - 1, the identity at m - 1
  *   fixed   alpha_tau_g1[0] | beta_tau_g1[0] | tau_g1[0] | beta_g2 | tau_g2[0]
- * The caller's guarantee is dg16_group_ntt's: every point has order r.  powers, out and every array in them: host
- * pointers only.  Synchronous; runs on channel 0.  log_m + 1 <= two-adicity of r and log_m <= 26, else
+ * The caller's guarantee is dg16_group_ntt's: every point has order r (`dg16_srs_verify` checks it).
+ * powers, out and every array in them: host pointers only.  Synchronous; runs on channel 0.  log_m + 1 <= two-adicity of r and log_m <= 26, else
  * DG16_ERR_BAD_ARG, as are a NULL pointer and another reduction; an unknown curve is DG16_ERR_BAD_CURVE. */
 int dg16_srs_prepare(dg16_ctx *ctx, int curve, unsigned log_m, int reduction, const dg16_srs_powers *powers,
                      dg16_srs_prepared *out);
+
+/* ---- Membership of points and verification of a powers-of-tau transcript ---------------------------------------------
+ * dg16_points_check: are n affine points (the layout of dg16_points_mul: x || y Montgomery limbs, identity = all-zero
+ * bytes) points of `group` (1 = G1, 2 = G2) of `curve`?  All three curves.  A point is BAD when a coordinate is not
+ * reduced (>= q), when it is off the equation of the curve or of its twist, or -- with subgroup = 1 -- when r P != O.
+ * The identity is a good point.  subgroup = 0 stops after the curve equation; BN254 G1 has cofactor one, so subgroup
+ * changes nothing there.  Bad points are a RESULT, not an error: the call returns DG16_OK with *n_bad their count and
+ * *first_bad the smallest bad index (n when there is none).  n = 0 is DG16_OK with *n_bad = 0.  One point per lane: the
+ * two cheap tests, then r P by a fixed chain over the non-adjacent form of the public constant r -- no table per point,
+ * no recoding, mixed additions.  points_affine, n_bad, first_bad: host pointers only.  Synchronous;
+ * runs on channel 0.  A large n runs in slices of the size dg16_ctx_set_points_mul_slice sets (default 2^16 points), and
+ * the device copy of a slice is temporary (DG16_ERR_OOM leaves the context usable).  A null pointer with n > 0, a NULL
+ * n_bad or first_bad, n >= 2^30 or a group other than 1 or 2 is DG16_ERR_BAD_ARG, an unknown curve DG16_ERR_BAD_CURVE. */
+int dg16_points_check(dg16_ctx *ctx, int curve, int group, const void *points_affine, size_t n,
+                      int subgroup /* 0: reduced coordinates and curve equation; 1: also order r */,
+                      size_t *n_bad, size_t *first_bad /* n when none */);
+
+/* Bits of dg16_srs_report::failed. */
+#define DG16_SRS_BAD_POINT 1u  /* a point with an unreduced coordinate, off its curve or outside the subgroup */
+#define DG16_SRS_IDENTITY 2u   /* tau_g1[0], tau_g1[1], tau_g2[0], tau_g2[1], alpha_tau_g1[0], beta_tau_g1[0] or beta_g2 is O */
+#define DG16_SRS_TAU_G1 4u     /* tau_g1 is not a geometric progression in the tau of tau_g2[1] */
+#define DG16_SRS_TAU_G2 8u     /* tau_g2 is not a geometric progression in the tau of tau_g1[1] */
+#define DG16_SRS_ALPHA 16u     /* alpha_tau_g1 is not one */
+#define DG16_SRS_BETA 32u      /* beta_tau_g1 is not one */
+#define DG16_SRS_BETA_G2 64u   /* beta_g2 and beta_tau_g1[0] hold different beta */
+typedef struct dg16_srs_report {
+  uint32_t failed;        /* 0 = accepted; bits above */
+  uint32_t bad_array;     /* with DG16_SRS_BAD_POINT: 0 tau_g1, 1 tau_g2, 2 alpha_tau_g1, 3 beta_tau_g1, 4 beta_g2 */
+  uint64_t bad_index;     /* the smallest bad index in that array (the first array that has one) */
+  uint64_t n_bad_points;  /* over all five arrays */
+} dg16_srs_report;
+/* Is this a powers-of-tau transcript (snarkjs `powersoftau verify`, without the contribution chain)?  BN254 and
+ * BLS12-381.  powers: dg16_srs_powers above, m = 2^log_m.  With T = tau_g1, U = tau_g2, A = alpha_tau_g1,
+ * B = beta_tau_g1 and coefficients rho_j, a bit of report->failed is CLEAR when:
+ *   DG16_SRS_BAD_POINT  dg16_points_check(subgroup = 1) finds nothing in any of the five arrays
+ *   DG16_SRS_IDENTITY   none of T_0, T_1, U_0, U_1, A_0, B_0, beta_g2 is the identity
+ *   DG16_SRS_TAU_G1     e(sum_{j < 2m-2} rho_j T_j, U_1) = e(sum_{j < 2m-2} rho_j T_(j+1), U_0)
+ *   DG16_SRS_TAU_G2     e(T_1, sum_{j < m-1} rho_j U_j) = e(T_0, sum_{j < m-1} rho_j U_(j+1))
+ *   DG16_SRS_ALPHA      e(sum_{j < m-1} rho_j A_j, U_1) = e(sum_{j < m-1} rho_j A_(j+1), U_0)
+ *   DG16_SRS_BETA       the same with B
+ *   DG16_SRS_BETA_G2    e(B_0, U_0) = e(T_0, beta_g2)
+ * Membership runs first: with DG16_SRS_BAD_POINT or DG16_SRS_IDENTITY set the five pairing checks are skipped and
+ * their bits stay clear (the sums use the endomorphism split and the pairing assumes subgroup points).  The eight sums
+ * (six in G1, two in G2) are the library's MSM on the device, the second of a pair on the same array shifted by one point; the five
+ * equalities are two Miller loops and one final exponentiation each, on the host.  The base points are whatever T_0
+ * and U_0 are: comparing them with the standard generators is a byte comparison for the caller.
+ * report->failed != 0 comes with DG16_OK: a bad transcript is a result, not an error.
+ * THE COEFFICIENTS ARE THE CALLER'S, as in dg16_groth16_verify_aggregate: coeffs = (2m - 2) x 16 bytes, each a
+ * little-endian unsigned 128-bit integer; the sums of m - 1 terms use the first m - 1.  The contract: the rho_j are
+ * independent and uniform in [1, 2^128), and they are chosen AFTER the transcript is fixed.  A transcript that fails an
+ * equation is then accepted with probability about 2^-128 per equation.  A zero coefficient is DG16_ERR_BAD_ARG,
+ * checked before any work.
+ * powers, coeffs, report and every array: host pointers only.  Synchronous; runs on channel 0; the device copies are
+ * temporary (DG16_ERR_OOM leaves the context usable).  log_m = 0, log_m > 26, log_m + 1 above the two-adicity of r or
+ * a NULL pointer: DG16_ERR_BAD_ARG.  DG16_BLS12_377 (no pairing here): DG16_ERR_UNSUPPORTED.  An unknown curve:
+ * DG16_ERR_BAD_CURVE. */
+int dg16_srs_verify(dg16_ctx *ctx, int curve, unsigned log_m, const dg16_srs_powers *powers,
+                    const void *coeffs /* (2m - 2) x 16 bytes */, dg16_srs_report *report);
 
 /* ---- Groth16 prover (single prover; the value the n-party run must equal) ------------------------
  * Replaces `Groth16::<E, CircomReduction>::create_proof_with_reduction_and_matrices` (third-party
