@@ -7,7 +7,9 @@
   * the native RCCL communicator at world size 1 (binding, communicator, grouped send / recv to self, all-gather) and
     dg16_groth16_prove_dist through it;
   * MpcNet's send_to / recv_from on the in-process LocalNet.
-The multi-process form (2 and 4 ranks sharing the GPU, gloo transport) is tests/test_gpu_two_rank.py."""
+The multi-process form (2 and 4 ranks sharing the GPU, gloo transport) is tests/test_gpu_two_rank.py.  The stage entry
+points on every shard shape (piece sizes, per-rank plans, structured values, the send buffers of every stage, the
+one-table twiddles) are tests/test_gpu_hdist_shapes.py, which uses dev_t, all_to_all and sharded_h from here."""
 
 import ctypes
 import threading
