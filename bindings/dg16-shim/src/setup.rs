@@ -232,6 +232,114 @@ where
     Ok(report)
 }
 
+/// `k * P_i` for ONE scalar and all the points (`dg16_points_scale`).  `in_subgroup`: the caller's word that every point
+/// has order r, which allows the endomorphism split; without it the call is correct for any point of the curve.
+pub fn points_scale<P>(points: &[Affine<P>], k: &P::ScalarField, in_subgroup: bool) -> Result<Vec<Affine<P>>, Dg16Error>
+where
+    P: Dg16Config,
+    P::BaseField: FieldBytes,
+{
+    let raw = pack_affine(points);
+    let mut out = vec![0u8; raw.len()];
+    let mut scalar = k.into_bigint().to_bytes_le();
+    scalar.resize(32, 0);
+    check(unsafe {
+        sys::dg16_points_scale(CTX.0, P::CURVE, P::GROUP, raw.as_ptr().cast(), scalar.as_ptr().cast(), points.len(),
+                               out.as_mut_ptr().cast(), if in_subgroup { 1 } else { 0 })
+    })?;
+    Ok(unpack_affine::<P>(&out))
+}
+
+/// One phase-2 contribution to `pk` (`dg16_groth16_contribute`): `delta_g1`, `delta_g2` times `delta`, `l_query` and
+/// `h_query` divided by it, everything else as it is.  THE RANDOMNESS IS THE CALLER'S: `delta` non-zero, uniform, and
+/// forgotten afterwards.  The caller vouches that the key's points have order r.
+pub fn contribute<E, P1, P2>(pk: &ProvingKey<E>, delta: &E::ScalarField) -> Result<ProvingKey<E>, Dg16Error>
+where
+    E: Pairing<G1Affine = Affine<P1>, G2Affine = Affine<P2>>,
+    P1: Dg16Config<ScalarField = E::ScalarField>,
+    P2: Dg16Config<ScalarField = E::ScalarField>,
+    P1::BaseField: FieldBytes,
+    P2::BaseField: FieldBytes,
+{
+    let f1 = 2 * <P1::BaseField as FieldBytes>::BYTES;
+    let (mut l, mut h) = (pack_affine(&pk.l_query), pack_affine(&pk.h_query));
+    let mut fixed = pack_affine(&[pk.vk.alpha_g1, pk.beta_g1, pk.delta_g1]);
+    fixed.extend(pack_affine(&[pk.vk.beta_g2, pk.vk.delta_g2]));
+    let mut d = delta.into_bigint().to_bytes_le();
+    d.resize(32, 0);
+    check(unsafe {
+        sys::dg16_groth16_contribute(CTX.0, P1::CURVE, pk.l_query.len(), pk.h_query.len(), l.as_ptr().cast(),
+                                     h.as_ptr().cast(), fixed.as_ptr().cast(), d.as_ptr().cast(), l.as_mut_ptr().cast(),
+                                     h.as_mut_ptr().cast(), fixed.as_mut_ptr().cast())
+    })?;
+    let mut out = pk.clone();
+    out.l_query = unpack_affine::<P1>(&l);
+    out.h_query = unpack_affine::<P1>(&h);
+    out.delta_g1 = unpack_affine::<P1>(&fixed[2 * f1..3 * f1])[0];
+    out.vk.delta_g2 = unpack_affine::<P2>(&fixed[3 * f1..])[1];
+    Ok(out)
+}
+
+struct PackedKey {
+    arrays: [Vec<u8>; 8],
+}
+impl PackedKey {
+    fn new<E, P1, P2>(pk: &ProvingKey<E>) -> Self
+    where
+        E: Pairing<G1Affine = Affine<P1>, G2Affine = Affine<P2>>,
+        P1: Dg16Config<ScalarField = E::ScalarField>,
+        P2: Dg16Config<ScalarField = E::ScalarField>,
+        P1::BaseField: FieldBytes,
+        P2::BaseField: FieldBytes,
+    {
+        let mut fixed = pack_affine(&[pk.vk.alpha_g1, pk.beta_g1, pk.delta_g1]);
+        fixed.extend(pack_affine(&[pk.vk.beta_g2, pk.vk.delta_g2]));
+        PackedKey {
+            arrays: [pack_affine(&pk.a_query), pack_affine(&pk.b_g1_query), pack_affine(&pk.b_g2_query),
+                     pack_affine(&pk.h_query), pack_affine(&pk.l_query), fixed, pack_affine(&[pk.vk.gamma_g2]),
+                     pack_affine(&pk.vk.gamma_abc_g1)],
+        }
+    }
+    fn raw(&self) -> sys::Dg16Groth16Key {
+        let p = |i: usize| self.arrays[i].as_ptr().cast();
+        sys::Dg16Groth16Key { a_query: p(0), b_g1_query: p(1), b_g2_query: p(2), h_query: p(3), l_query: p(4),
+                              fixed_points: p(5), gamma_g2: p(6), gamma_abc_g1: p(7) }
+    }
+}
+
+/// Is `after` the key `before` with delta replaced by d * delta for some d (`dg16_groth16_verify_contribution`)?
+/// `coeffs`: max(l_query.len(), h_query.len()) integers in [1, 2^128), independent, uniform and drawn AFTER both keys
+/// were fixed -- the caller's randomness.  `report.failed == 0` accepts; its bits are `sys::DG16_P2_*`.  A rejected key is
+/// `Ok` with the bits set; a zero coefficient is an error.  Not checked: a contributor's proof of knowledge and a
+/// transcript's hash chain.
+pub fn verify_contribution<E, P1, P2>(before: &ProvingKey<E>, after: &ProvingKey<E>, coeffs: &[u128])
+    -> Result<sys::Dg16Phase2Report, Dg16Error>
+where
+    E: Pairing<G1Affine = Affine<P1>, G2Affine = Affine<P2>>,
+    P1: Dg16Config<ScalarField = E::ScalarField>,
+    P2: Dg16Config<ScalarField = E::ScalarField>,
+    P1::BaseField: FieldBytes,
+    P2::BaseField: FieldBytes,
+{
+    let (ni, nv, m) = (before.vk.gamma_abc_g1.len(), before.a_query.len(), before.h_query.len());
+    if after.vk.gamma_abc_g1.len() != ni || after.a_query.len() != nv || after.h_query.len() != m
+        || before.l_query.len() != nv - ni || after.l_query.len() != nv - ni || before.b_g1_query.len() != nv
+        || after.b_g1_query.len() != nv || before.b_g2_query.len() != nv || after.b_g2_query.len() != nv
+        || coeffs.len() != (nv - ni).max(m)
+    {
+        return Err(Dg16Error::Status(sys::DG16_ERR_BAD_ARG,
+                                     "keys of different shapes, or not max(l_query, h_query) coefficients".into()));
+    }
+    let (kb, ka) = (PackedKey::new(before), PackedKey::new(after));
+    let (rb, ra) = (kb.raw(), ka.raw());
+    let rho: Vec<u8> = coeffs.iter().flat_map(|c| c.to_le_bytes()).collect();
+    let mut report = sys::Dg16Phase2Report::default();
+    check(unsafe {
+        sys::dg16_groth16_verify_contribution(CTX.0, P1::CURVE, ni, nv, m, &rb, &ra, rho.as_ptr().cast(), &mut report)
+    })?;
+    Ok(report)
+}
+
 /// The key of `m` computed in the exponent from `srs` (`dg16_groth16_setup_srs`): gamma = delta = 1, no trapdoor.
 /// `in_subgroup` passes DG16_F_BASES_IN_SUBGROUP (the endomorphism split of the coefficients).
 pub fn setup_from_srs<E, P1, P2>(m: &ConstraintMatrices<E::ScalarField>, srs: &Srs<E>, in_subgroup: bool)

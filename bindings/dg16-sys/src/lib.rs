@@ -168,6 +168,34 @@ pub const DG16_SRS_TAU_G2: u32 = 8;
 pub const DG16_SRS_ALPHA: u32 = 16;
 pub const DG16_SRS_BETA: u32 = 32;
 pub const DG16_SRS_BETA_G2: u32 = 64;
+/// `dg16_groth16_key`: the eight outputs of `dg16_groth16_setup` as HOST pointers (`dg16_groth16_verify_contribution`)
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct Dg16Groth16Key {
+    pub a_query: *const c_void,
+    pub b_g1_query: *const c_void,
+    pub b_g2_query: *const c_void,
+    pub h_query: *const c_void,
+    pub l_query: *const c_void,
+    pub fixed_points: *const c_void,
+    pub gamma_g2: *const c_void,
+    pub gamma_abc_g1: *const c_void,
+}
+/// `dg16_phase2_report`: what `dg16_groth16_verify_contribution` found (failed = 0: accepted; the DG16_P2_* bits below)
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default, PartialEq, Eq)]
+pub struct Dg16Phase2Report {
+    pub failed: u32,
+    pub bad_array: u32,
+    pub bad_index: u64,
+    pub n_bad_points: u64,
+}
+pub const DG16_P2_BAD_POINT: u32 = 1;
+pub const DG16_P2_IDENTITY: u32 = 2;
+pub const DG16_P2_CHANGED: u32 = 4;
+pub const DG16_P2_DELTA: u32 = 8;
+pub const DG16_P2_L: u32 = 16;
+pub const DG16_P2_H: u32 = 32;
 /// `dg16_srs_prepared`: the caller-allocated HOST buffers `dg16_srs_prepare` fills, laid out as the arrays of `dg16_srs`
 #[repr(C)]
 #[derive(Clone, Copy, Debug)]
@@ -275,6 +303,17 @@ extern "C" {
                              subgroup: c_int, n_bad: *mut usize, first_bad: *mut usize) -> c_int;
     pub fn dg16_srs_verify(ctx: *mut Dg16Ctx, curve: c_int, log_m: c_uint, powers: *const Dg16SrsPowers,
                            coeffs: *const c_void, report: *mut Dg16SrsReport) -> c_int;
+    // phase 2 of the key ceremony: one scalar times n points, a contribution to delta, and the check that one key is
+    // another with delta moved; host pointers only, synchronous, channel 0.  A rejected key is a result.
+    pub fn dg16_points_scale(ctx: *mut Dg16Ctx, curve: c_int, group: c_int, points_affine: *const c_void,
+                             scalar: *const c_void, n: usize, out_affine: *mut c_void, in_subgroup: c_int) -> c_int;
+    pub fn dg16_groth16_contribute(ctx: *mut Dg16Ctx, curve: c_int, n_l: usize, n_h: usize, l_query: *const c_void,
+                                   h_query: *const c_void, fixed_points: *const c_void, delta: *const c_void,
+                                   l_out: *mut c_void, h_out: *mut c_void, fixed_out: *mut c_void) -> c_int;
+    pub fn dg16_groth16_verify_contribution(ctx: *mut Dg16Ctx, curve: c_int, num_inputs: usize, num_vars: usize,
+                                            domain_size: usize, before: *const Dg16Groth16Key,
+                                            after: *const Dg16Groth16Key, coeffs: *const c_void,
+                                            report: *mut Dg16Phase2Report) -> c_int;
     pub fn dg16_to_affine(ctx: *mut Dg16Ctx, curve: c_int, group: c_int, jac: *const c_void, out: *mut c_void,
                           n: usize, flags: c_uint, channel: c_int) -> c_int;
     // resident bases (a CRS is uploaded once; msm over its window tables)

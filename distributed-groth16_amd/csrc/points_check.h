@@ -215,6 +215,15 @@ template <> void points_check_run<1>(Call&, int, const void*, size_t, size_t, in
 template <> void points_check_run<2>(Call&, int, const void*, size_t, size_t, int, pchk::CheckResult*);
 template <> void srs_verify_run<0>(Call&, unsigned, const dg16_srs_powers*, const void*, dg16_srs_report*);
 template <> void srs_verify_run<1>(Call&, unsigned, const dg16_srs_powers*, const void*, dg16_srs_report*);
+// the checks behind dg16_groth16_verify_contribution (BN254, BLS12-381), beside srs_verify_run whose membership stage,
+// sums and pairing equality they share; argument checks are the caller's
+template <int CURVE>
+void phase2_verify_run(Call& k, size_t num_inputs, size_t num_vars, size_t domain_size, const dg16_groth16_key* before,
+                       const dg16_groth16_key* after, const void* coeffs, dg16_phase2_report* report);
+template <> void phase2_verify_run<0>(Call&, size_t, size_t, size_t, const dg16_groth16_key*, const dg16_groth16_key*,
+                                      const void*, dg16_phase2_report*);
+template <> void phase2_verify_run<1>(Call&, size_t, size_t, size_t, const dg16_groth16_key*, const dg16_groth16_key*,
+                                      const void*, dg16_phase2_report*);
 
 }  // namespace dg16
 #endif

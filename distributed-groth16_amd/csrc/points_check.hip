@@ -1,4 +1,5 @@
-// C ABI of the membership check and of the transcript verifier (include/dg16.h): dg16_points_check, dg16_srs_verify.
+// C ABI of the membership check, of the transcript verifier and of the verifier of a phase-2 contribution
+// (include/dg16.h): dg16_points_check, dg16_srs_verify, dg16_groth16_verify_contribution.
 // Argument checks, the device copies of the host arrays and the dispatch on the curve; the kernel and the transcript
 // checks live in the per-curve objects (points_check_curve.hip).  Both calls take host pointers only, run on channel 0
 // and are synchronous; their device buffers are freed on every path.
@@ -90,6 +91,37 @@ int dg16_srs_verify(dg16_ctx* ctx, int curve, unsigned log_m, const dg16_srs_pow
     Call k(ctx, 0);
     if (curve == DG16_BN254) srs_verify_run<0>(k, log_m, powers, coeffs, report);
     else srs_verify_run<1>(k, log_m, powers, coeffs, report);
+    k.finish();
+    DG_HIP(hipStreamSynchronize(k.s()));
+  });
+}
+
+int dg16_groth16_verify_contribution(dg16_ctx* ctx, int curve, size_t num_inputs, size_t num_vars, size_t domain_size,
+                                     const dg16_groth16_key* before, const dg16_groth16_key* after, const void* coeffs,
+                                     dg16_phase2_report* report) {
+  if (!ctx) return DG16_ERR_BAD_ARG;
+  return guarded(ctx, [&] {
+    DG_REQUIRE(curve >= 0 && curve <= 2, DG16_ERR_BAD_CURVE, "unknown curve id");
+    DG_REQUIRE(curve != DG16_BLS12_377, DG16_ERR_UNSUPPORTED, "contribution verification: BN254 and BLS12-381 only");
+    DG_REQUIRE(before && after && coeffs && report, DG16_ERR_BAD_ARG, "null argument");
+    constexpr size_t kMax = (size_t)1 << 28;
+    DG_REQUIRE(num_inputs >= 1 && num_inputs <= num_vars && num_vars < kMax && domain_size >= 1 && domain_size < kMax,
+               DG16_ERR_BAD_ARG, "need 1 <= num_inputs <= num_vars < 2^28 and 1 <= domain_size < 2^28");
+    const size_t n_l = num_vars - num_inputs;
+    for (const dg16_groth16_key* key : {before, after})
+      DG_REQUIRE(key->a_query && key->b_g1_query && key->b_g2_query && key->h_query && (key->l_query || !n_l) &&
+                     key->fixed_points && key->gamma_g2 && key->gamma_abc_g1,
+                 DG16_ERR_BAD_ARG, "null array in a key");
+    const size_t n_coeff = n_l > domain_size ? n_l : domain_size;
+    const uint8_t* c = (const uint8_t*)coeffs;
+    for (size_t j = 0; j < n_coeff; j++) {
+      uint8_t any = 0;
+      for (int b = 0; b < 16; b++) any |= c[16 * j + b];
+      DG_REQUIRE(any, DG16_ERR_BAD_ARG, "a coefficient is zero");
+    }
+    Call k(ctx, 0);
+    if (curve == DG16_BN254) phase2_verify_run<0>(k, num_inputs, num_vars, domain_size, before, after, coeffs, report);
+    else phase2_verify_run<1>(k, num_inputs, num_vars, domain_size, before, after, coeffs, report);
     k.finish();
     DG_HIP(hipStreamSynchronize(k.s()));
   });

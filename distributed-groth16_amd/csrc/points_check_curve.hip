@@ -1,5 +1,6 @@
 // Per-curve object of the membership check (points_check.h): points_check_kernel for G1 and G2 of curve DG_CURVE, and --
-// for the curves that have a pairing here (BN254, BLS12-381) -- the transcript checks of dg16_srs_verify.
+// for the curves that have a pairing here (BN254, BLS12-381) -- the transcript checks of dg16_srs_verify and the checks
+// of a phase-2 contribution (dg16_groth16_verify_contribution), which run the same three stages.
 //
 //   membership   the five arrays are copied to the device whole (the sums read them anyway) and checked with
 //                subgroup = 1, one result pair per array; the seven heads are compared with the identity on the host
@@ -147,6 +148,95 @@ void srs_verify_run<DG_CURVE>(Call& k, unsigned log_m, const dg16_srs_powers* pw
   if (!pairings_equal(sums.g1[2], u1, sums.g1[3], u0)) report->failed |= DG16_SRS_ALPHA;
   if (!pairings_equal(sums.g1[4], u1, sums.g1[5], u0)) report->failed |= DG16_SRS_BETA;
   if (!pairings_equal(b0, u0, t0, bg2)) report->failed |= DG16_SRS_BETA_G2;
+}
+
+// dg16_groth16_verify_contribution: membership of the eight arrays a contribution rewrites, the byte comparison of the
+// ones it does not, four sums (msm_launch) and three equalities -- the stages of srs_verify_run on another statement
+template <>
+void phase2_verify_run<DG_CURVE>(Call& k, size_t num_inputs, size_t num_vars, size_t domain_size,
+                                 const dg16_groth16_key* before, const dg16_groth16_key* after, const void* coeffs,
+                                 dg16_phase2_report* report) {
+  constexpr size_t g1b = sizeof(Affine<Fq>), g2b = sizeof(Affine<Fq2>);
+  const size_t n_l = num_vars - num_inputs, n_h = domain_size;
+  const dg16_groth16_key* key[2] = {before, after};
+  memset(report, 0, sizeof *report);
+
+  // L, H, D1, D2 of `before`, then of `after`
+  const void* host[8];
+  const size_t count[8] = {n_l, n_h, 1, 1, n_l, n_h, 1, 1};
+  const int group[8] = {1, 1, 1, 2, 1, 1, 1, 2};
+  for (int s = 0; s < 2; s++) {
+    const char* f = (const char*)key[s]->fixed_points;
+    host[4 * s] = key[s]->l_query;
+    host[4 * s + 1] = key[s]->h_query;
+    host[4 * s + 2] = f + 2 * g1b;
+    host[4 * s + 3] = f + 3 * g1b + g2b;
+  }
+  DeviceBuffers buf;
+  void* dev[8];
+  for (int a = 0; a < 8; a++) {
+    const size_t bytes = count[a] * (group[a] == 1 ? g1b : g2b);
+    dev[a] = buf.get(bytes);
+    if (bytes) DG_HIP(hipMemcpyAsync(dev[a], host[a], bytes, hipMemcpyHostToDevice, k.s()));
+  }
+  // ---- membership ----
+  pchk::CheckResult res[8];
+  for (int a = 0; a < 8; a++) res[a] = {0ull, (unsigned long long)count[a]};
+  pchk::CheckResult* dres = (pchk::CheckResult*)buf.get(sizeof res);
+  DG_HIP(hipMemcpyAsync(dres, res, sizeof res, hipMemcpyHostToDevice, k.s()));
+  k.begin_dominant();
+  for (int a = 0; a < 8; a++) points_check_run<DG_CURVE>(k, group[a], dev[a], count[a], 0, 1, dres + a);
+  k.end_dominant();
+  DG_HIP(hipMemcpyAsync(res, dres, sizeof res, hipMemcpyDeviceToHost, k.s()));
+  DG_HIP(hipStreamSynchronize(k.s()));
+  bool found = false;
+  for (int a = 0; a < 8; a++) {
+    report->n_bad_points += res[a].n_bad;
+    if (res[a].n_bad && !found) {
+      found = true;
+      report->bad_array = (uint32_t)a;
+      report->bad_index = res[a].first_bad;
+    }
+  }
+  if (found) report->failed |= DG16_P2_BAD_POINT;
+  if (all_zero(host[2], g1b) || all_zero(host[3], g2b) || all_zero(host[6], g1b) || all_zero(host[7], g2b))
+    report->failed |= DG16_P2_IDENTITY;
+  // ---- what a contribution leaves alone ----
+  const char* f0 = (const char*)before->fixed_points;
+  const char* f1 = (const char*)after->fixed_points;
+  if (memcmp(before->a_query, after->a_query, num_vars * g1b) ||
+      memcmp(before->b_g1_query, after->b_g1_query, num_vars * g1b) ||
+      memcmp(before->b_g2_query, after->b_g2_query, num_vars * g2b) ||
+      memcmp(before->gamma_g2, after->gamma_g2, g2b) ||
+      memcmp(before->gamma_abc_g1, after->gamma_abc_g1, num_inputs * g1b) || memcmp(f0, f1, 2 * g1b) ||
+      memcmp(f0 + 3 * g1b, f1 + 3 * g1b, g2b))
+    report->failed |= DG16_P2_CHANGED;
+  if (report->failed & (DG16_P2_BAD_POINT | DG16_P2_IDENTITY)) return;
+
+  // ---- the four sums: rho L, rho H, rho L', rho H' ----
+  const size_t n_coeff = n_l > n_h ? n_l : n_h;
+  std::vector<uint32_t> wide(n_coeff * 8, 0u);
+  for (size_t j = 0; j < n_coeff; j++) memcpy(&wide[8 * j], (const char*)coeffs + 16 * j, 16);
+  void* dscal = buf.get(n_coeff * 32);
+  DG_HIP(hipMemcpyAsync(dscal, wide.data(), n_coeff * 32, hipMemcpyHostToDevice, k.s()));
+  char* dsum = (char*)buf.get(4 * g1b);
+  Affine<Fq> sums[4];
+  const int sum_of[4] = {0, 1, 4, 5};
+  for (int s = 0; s < 4; s++)
+    if (count[sum_of[s]]) msm_launch(k, DG_CURVE, 1, dev[sum_of[s]], dscal, count[sum_of[s]], 2u, true, dsum + s * g1b);
+  DG_HIP(hipMemcpyAsync(sums, dsum, sizeof sums, hipMemcpyDeviceToHost, k.s()));
+  DG_HIP(hipStreamSynchronize(k.s()));
+
+  // ---- the three equalities ----
+  Affine<Fq> d1[2];
+  Affine<Fq2> d2[2];
+  for (int s = 0; s < 2; s++) {
+    memcpy(&d1[s], host[4 * s + 2], g1b);
+    memcpy(&d2[s], host[4 * s + 3], g2b);
+  }
+  if (!pairings_equal(d1[1], d2[0], d1[0], d2[1])) report->failed |= DG16_P2_DELTA;
+  if (n_l && !pairings_equal(sums[2], d2[1], sums[0], d2[0])) report->failed |= DG16_P2_L;
+  if (!pairings_equal(sums[3], d2[1], sums[1], d2[0])) report->failed |= DG16_P2_H;
 }
 #endif
 

@@ -16,6 +16,13 @@ csrc/group_ntt_curve.hip; snarkjs' `powersoftau prepare phase2`):
 
     srs = srs_from_powers(ctx, "bn254", log_m, tau_g1, tau_g2, alpha_tau_g1, beta_tau_g1, beta_g2)
 
+Such a key becomes one anybody may use through phase 2 of the ceremony -- every participant multiplies delta by a secret
+of their own (`dg16_groth16_contribute`, csrc/points_scale.h), and anybody can check the result against the circuit and
+the reference string (`dg16_groth16_verify_contribution`; snarkjs' `zkey contribute` and the key part of `zkey verify`):
+
+    params = contribute(ctx, params, 1 + secrets.randbelow(r - 1))      # the contributor forgets the secret
+    report = verify_parameters(ctx, "bn254", r1cs, srs, params)         # report.accepted
+
 The trapdoor (alpha, beta, gamma, delta, tau) is drawn from `secrets` unless the caller passes one; it is returned with
 the parameters only when it was passed in.  torch is the device-memory plumbing; there is no CPU path."""
 
@@ -397,3 +404,92 @@ def generate_parameters_from_srs(ctx, curve, r1cs, srs, reduction="circom", in_s
     params = Parameters(curve, nc, ni, nv, log_m, arrays, trapdoor=None)
     params.reduction = reduction
     return params
+
+
+def contribute(ctx, params, delta):
+    """One phase-2 contribution to a key (`dg16_groth16_contribute`; snarkjs' `zkey contribute` without its transcript):
+    l_query and h_query are divided by d = delta, delta_g1 and delta_g2 multiplied by it, every other array is shared
+    with `params`.  THE RANDOMNESS IS THE CALLER'S: delta is an int in [1, r), uniform, and to be forgotten afterwards --
+    the key is sound as long as ONE contributor did.  The caller vouches that the key's points have order r.  The three
+    arrays go through the host (`.host()`) and are uploaded again.  Returns new Parameters with `reduction` kept and
+    trapdoor None."""
+    import torch
+    curve = params.curve
+    delta = int(delta)
+    if not 0 < delta < FR_MODULUS[curve]:
+        raise ValueError("delta must be non-zero and below r")
+    l, h, f = ctx.groth16_contribute(curve, params.host("l_query"), params.host("h_query"),
+                                     params.host("fixed_points").reshape(-1), delta)
+    dev = params.fixed_points.device
+
+    def up(x):
+        if x.size == 0:
+            return torch.zeros(16, dtype=torch.uint8, device=dev)[:0]
+        return torch.from_numpy(x.view(np.uint8).reshape(-1)).to(dev)
+
+    new = {"l_query": up(l), "h_query": up(h), "fixed_points": up(f)}
+    arrays = [new.get(n, getattr(params, n)) for n in Parameters.NAMES]
+    out = Parameters(curve, params.num_constraints, params.num_inputs, params.num_vars, params.log_m, arrays,
+                     trapdoor=None)
+    out.reduction = getattr(params, "reduction", None)
+    return out
+
+
+class Phase2Report:
+    """What `verify_contribution` found: `.accepted`, the word `.failed` (0 = accepted) and a name per bit of it, the
+    bits of dg16_phase2_report in include/dg16.h.  With BAD_POINT: `.bad_array` (the name of the first array that holds a
+    bad point), `.bad_index` (the smallest bad index in it) and `.n_bad_points` (over all eight arrays)."""
+
+    BAD_POINT, IDENTITY, CHANGED, DELTA, L, H = 1, 2, 4, 8, 16, 32
+    NAMES = {1: "bad_point", 2: "identity", 4: "changed", 8: "delta", 16: "l", 32: "h"}
+    ARRAYS = ("before.l_query", "before.h_query", "before.delta_g1", "before.delta_g2",
+              "after.l_query", "after.h_query", "after.delta_g1", "after.delta_g2")
+
+    def __init__(self, failed, bad_array=0, bad_index=0, n_bad_points=0):
+        self.failed = int(failed)
+        self.n_bad_points = int(n_bad_points)
+        self.bad_array = self.ARRAYS[bad_array] if self.failed & self.BAD_POINT else None
+        self.bad_index = int(bad_index) if self.failed & self.BAD_POINT else None
+        for bit, name in self.NAMES.items():
+            setattr(self, name, bool(self.failed & bit))
+
+    @property
+    def accepted(self):
+        return self.failed == 0
+
+    @property
+    def reasons(self):
+        return [name for bit, name in self.NAMES.items() if self.failed & bit]
+
+    def __repr__(self):
+        return "Phase2Report(accepted=%r, failed=%d %r)" % (self.accepted, self.failed, self.reasons)
+
+
+def verify_contribution(ctx, before, after, coeffs=None):
+    """Is `after` the key `before` with delta replaced by d * delta for some d (`dg16_groth16_verify_contribution`)?  Both
+    are Parameters of the same system.  Every point of l_query, h_query, delta_g1, delta_g2 of both keys must be
+    reduced, on its curve and of order r; no delta may be the identity; the arrays a contribution leaves alone must be
+    byte-equal; and the deltas, l_query and h_query must have moved by one d -- each decided by one pairing equation,
+    the last two on a random linear combination.  coeffs: uint64 [max(num_vars - num_inputs, domain_size)][2],
+    independent and uniform in [1, 2^128) and drawn AFTER both keys were fixed; None draws them with
+    `verify.random_coefficients`.  A key that fails an equation is then accepted with probability about 2^-128.  Not
+    checked: a contributor's proof of knowledge and a transcript's hash chain.  BN254 and BLS12-381.  Returns a
+    Phase2Report."""
+    shape = lambda p: (p.curve, p.num_inputs, p.num_vars, p.domain_size)      # noqa: E731
+    if shape(before) != shape(after):
+        raise ValueError("the keys are of different systems: %r, %r" % (shape(before), shape(after)))
+    if coeffs is None:
+        from .verify import random_coefficients
+        coeffs = random_coefficients(max(before.num_vars - before.num_inputs, before.domain_size))
+    keys = [[p.host(n).reshape(-1) for n in Parameters.NAMES] for p in (before, after)]
+    return Phase2Report(*ctx.groth16_verify_contribution(before.curve, before.num_inputs, before.num_vars,
+                                                         before.domain_size, keys[0], keys[1], coeffs))
+
+
+def verify_parameters(ctx, curve, r1cs, srs, params, reduction="circom", coeffs=None):
+    """Is `params` a key of THIS R1CS over THIS reference string (the key part of snarkjs' `zkey verify`)?  The
+    uncontributed key is computed again (`generate_parameters_from_srs`, in_subgroup as the caller of that would pass
+    for a verified string: False here, the plain loops) and `params` is held against it with `verify_contribution`;
+    the relation is transitive in d, so any number of contributions is covered.  Returns a Phase2Report."""
+    initial = generate_parameters_from_srs(ctx, curve, r1cs, srs, reduction=reduction)
+    return verify_contribution(ctx, initial, params, coeffs=coeffs)

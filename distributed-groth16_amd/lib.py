@@ -70,6 +70,16 @@ class SrsReportC(ctypes.Structure):       # dg16_srs_report
                 ("n_bad_points", ctypes.c_uint64)]
 
 
+class Groth16Key(ctypes.Structure):       # dg16_groth16_key
+    _fields_ = [(n, ctypes.c_void_p) for n in ("a_query", "b_g1_query", "b_g2_query", "h_query", "l_query",
+                                               "fixed_points", "gamma_g2", "gamma_abc_g1")]
+
+
+class Phase2ReportC(ctypes.Structure):    # dg16_phase2_report
+    _fields_ = [("failed", ctypes.c_uint32), ("bad_array", ctypes.c_uint32), ("bad_index", ctypes.c_uint64),
+                ("n_bad_points", ctypes.c_uint64)]
+
+
 class PkInfo(ctypes.Structure):           # dg16_pk_info
     _fields_ = [("n_ab", ctypes.c_uint64), ("n_l", ctypes.c_uint64), ("n_h", ctypes.c_uint64),
                 ("c_ab", ctypes.c_uint32), ("c_l", ctypes.c_uint32), ("c_h", ctypes.c_uint32),
@@ -278,6 +288,10 @@ def load():
     L.dg16_srs_prepare.argtypes = [vp, i, u, i, ctypes.POINTER(SrsPowers), ctypes.POINTER(SrsPrepared)]
     L.dg16_points_check.argtypes = [vp, i, i, vp, sz, i, ctypes.POINTER(sz), ctypes.POINTER(sz)]
     L.dg16_srs_verify.argtypes = [vp, i, u, ctypes.POINTER(SrsPowers), vp, ctypes.POINTER(SrsReportC)]
+    L.dg16_points_scale.argtypes = [vp, i, i, vp, vp, sz, vp, i]
+    L.dg16_groth16_contribute.argtypes = [vp, i, sz, sz, vp, vp, vp, vp, vp, vp, vp]
+    L.dg16_groth16_verify_contribution.argtypes = [vp, i, sz, sz, sz, ctypes.POINTER(Groth16Key),
+                                                   ctypes.POINTER(Groth16Key), vp, ctypes.POINTER(Phase2ReportC)]
     _lib = L
     return L
 
@@ -304,7 +318,8 @@ EXPORTED = ["dg16_ctx_create", "dg16_ctx_destroy", "dg16_last_error", "dg16_set_
             "dg16_vk_create", "dg16_vk_destroy", "dg16_groth16_verify_batch", "dg16_groth16_verify_aggregate",
             "dg16_points_mul", "dg16_ctx_set_points_mul_slice", "dg16_groth16_rerandomize",
             "dg16_groth16_setup_srs", "dg16_setup_srs_limits", "dg16_group_ntt", "dg16_srs_prepare",
-            "dg16_points_check", "dg16_srs_verify"]
+            "dg16_points_check", "dg16_srs_verify", "dg16_points_scale", "dg16_groth16_contribute",
+            "dg16_groth16_verify_contribution"]
 
 
 def _ptr(x):
@@ -314,6 +329,19 @@ def _ptr(x):
     if isinstance(x, np.ndarray):
         return x.ctypes.data_as(ctypes.c_void_p)
     return ctypes.c_void_p(int(x))
+
+
+def _scalar32(x):
+    """An int or 32 bytes as a uint64 [4] array -> the 32 canonical little-endian bytes of one scalar."""
+    if isinstance(x, np.ndarray):
+        x = np.ascontiguousarray(x, dtype=np.uint64).reshape(-1)
+        if x.size != 4:
+            raise ValueError("a scalar is 32 bytes")
+        return x
+    x = int(x)
+    if not 0 <= x < 1 << 256:
+        raise ValueError("a scalar is 32 bytes")
+    return np.frombuffer(x.to_bytes(32, "little"), dtype=np.uint64).copy()
 
 
 class ResidentBases:
@@ -698,6 +726,75 @@ class Context:
         pw = SrsPowers(*[a.ctypes.data for a in ins])
         rep = SrsReportC()
         self._chk(self.L.dg16_srs_verify(self.h, CURVES[curve], log_m, ctypes.byref(pw), _ptr(coeffs), ctypes.byref(rep)))
+        return rep.failed, rep.bad_array, rep.bad_index, rep.n_bad_points
+
+    def points_scale(self, curve, group, points, scalar, in_subgroup=False, out=None):
+        """out[i] = scalar * points[i] (`dg16_points_scale`): ONE scalar, an int below 2^255 or 32 canonical bytes as a
+        uint64 [4] array, for all the affine points (host array, identity = zeros).  Correct for any point of the curve;
+        in_subgroup=True (every point is in the order-r subgroup) lets the library split the scalar with the curve's
+        endomorphism.  out: None for a new array, or a host array of the same shape (it may be `points`).  Synchronous."""
+        nl = FQ_LIMBS64[curve] * 2 * (2 if group == 2 else 1)
+        points = np.ascontiguousarray(points, dtype=np.uint64).reshape(-1, nl)
+        k = _scalar32(scalar)
+        if out is None:
+            out = np.zeros_like(points)
+        elif not (isinstance(out, np.ndarray) and out.dtype == np.uint64 and out.flags.c_contiguous
+                  and out.size == points.size):
+            raise ValueError("out must be a contiguous uint64 array of the points' size")
+        n = points.shape[0]
+        self._chk(self.L.dg16_points_scale(self.h, CURVES[curve], group, _ptr(points) if n else None, _ptr(k), n,
+                                           _ptr(out) if n else None, int(bool(in_subgroup))))
+        return out
+
+    def groth16_contribute(self, curve, l_query, h_query, fixed_points, delta, in_place=False):
+        """`dg16_groth16_contribute`: one phase-2 contribution d = delta (an int in [1, r), the CALLER's randomness) to
+        the arrays of a key (host arrays): -> (l_query / d, h_query / d, fixed_points with delta_g1 and delta_g2 times
+        d).  The caller vouches that the key's points have order r.  in_place=True writes into the given arrays (they
+        must be contiguous uint64 arrays) and returns them.  Synchronous."""
+        fq = FQ_LIMBS64[curve]
+        ins = [np.ascontiguousarray(x, dtype=np.uint64) for x in (l_query, h_query, fixed_points)]
+        if ins[2].size != 3 * 2 * fq + 2 * 4 * fq:
+            raise ValueError("fixed_points = alpha_g1 | beta_g1 | delta_g1 | beta_g2 | delta_g2")
+        if ins[0].size % (2 * fq) or ins[1].size % (2 * fq):
+            raise ValueError("l_query and h_query hold G1 points")
+        if in_place and any(a is not b for a, b in zip(ins, (l_query, h_query, fixed_points))):
+            raise ValueError("in_place needs contiguous uint64 arrays")
+        outs = ins if in_place else [np.zeros_like(a) for a in ins]
+        n_l, n_h = ins[0].size // (2 * fq), ins[1].size // (2 * fq)
+        self._chk(self.L.dg16_groth16_contribute(self.h, CURVES[curve], n_l, n_h, _ptr(ins[0]) if n_l else None,
+                                                 _ptr(ins[1]) if n_h else None, _ptr(ins[2]), _ptr(_scalar32(delta)),
+                                                 _ptr(outs[0]) if n_l else None, _ptr(outs[1]) if n_h else None,
+                                                 _ptr(outs[2])))
+        return tuple(outs)
+
+    def groth16_verify_contribution(self, curve, num_inputs, num_vars, domain_size, before, after, coeffs):
+        """`dg16_groth16_verify_contribution`: is the key `after` the key `before` with delta replaced by d * delta for
+        some d?  before / after: the eight host arrays a_query, b_g1_query, b_g2_query, h_query, l_query, fixed_points,
+        gamma_g2, gamma_abc_g1 (the order of `groth16_setup`'s outputs).  coeffs: uint64 [max(num_vars - num_inputs,
+        domain_size)][2], little-endian 128-bit integers in [1, 2^128) -- independent, uniform and drawn AFTER both keys
+        were fixed (`verify.random_coefficients`).  Returns (failed, bad_array, bad_index, n_bad_points); failed = 0
+        accepts, its bits are the DG16_P2_* of the header (`keygen.Phase2Report` names them).  Synchronous."""
+        fq = FQ_LIMBS64[curve]
+        n_l = num_vars - num_inputs
+        want = (num_vars * 2 * fq, num_vars * 2 * fq, num_vars * 4 * fq, domain_size * 2 * fq, n_l * 2 * fq,
+                3 * 2 * fq + 2 * 4 * fq, 4 * fq, num_inputs * 2 * fq)
+        keys = []
+        for which, key in (("before", before), ("after", after)):
+            arrs = [np.ascontiguousarray(a, dtype=np.uint64) for a in key]
+            if len(arrs) != 8:
+                raise ValueError("a key is eight arrays")
+            for name, a, size in zip(Groth16Key._fields_, arrs, want):
+                if a.size != size:
+                    raise ValueError("%s.%s must hold %d words" % (which, name[0], size))
+            keys.append(arrs)
+        coeffs = np.ascontiguousarray(coeffs, dtype=np.uint64)
+        if coeffs.size != max(n_l, domain_size) * 2:
+            raise ValueError("coeffs must hold %d 128-bit integers" % max(n_l, domain_size))
+        ks = [Groth16Key(*[a.ctypes.data if a.size else None for a in arrs]) for arrs in keys]
+        rep = Phase2ReportC()
+        self._chk(self.L.dg16_groth16_verify_contribution(self.h, CURVES[curve], num_inputs, num_vars, domain_size,
+                                                          ctypes.byref(ks[0]), ctypes.byref(ks[1]), _ptr(coeffs),
+                                                          ctypes.byref(rep)))
         return rep.failed, rep.bad_array, rep.bad_index, rep.n_bad_points
 
     def to_affine(self, curve, group, jac, channel=0):

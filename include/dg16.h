@@ -879,6 +879,91 @@ int dg16_ctx_set_points_mul_slice(dg16_ctx *ctx, size_t products);
 int dg16_groth16_rerandomize(dg16_ctx *ctx, const dg16_vk *vk, const void *proofs_affine, size_t n_proofs,
                              const void *r1_r2, unsigned flags, void *proofs_out, int channel);
 
+/* ---- Phase 2 of the key ceremony: one scalar times n points, a contribution to delta, and its verification ----------
+ * dg16_groth16_setup_srs ends at a key with gamma = delta = 1, which must not be deployed: with delta public the
+ * l_query and h_query terms are unprotected.  The reference's recipe for a production key
+ * (scripts/phase2_proving_key.sh:16-20) is `groth16 setup` -> `zkey contribute` -> `zkey verify`; these are the last two.
+ *
+ * dg16_points_scale: out[i] = k * points[i], i < n, ONE scalar for all points.  Layouts, curves and groups are those of
+ * dg16_points_mul.  scalar: 32 bytes, a canonical little-endian integer below 2^255 (DG16_ERR_BAD_ARG otherwise).  The
+ * scalar is split and recoded on the host once -- a width-5 non-adjacent form per part -- and every lane walks the same
+ * digits: a zero digit is a doubling and nothing else, the table holds the odd multiples only.  The
+ * split rule is dg16_msm's: the endomorphism split for the cofactor-one group (BN254 G1) always, for the others only
+ * with in_subgroup = 1, the caller's word that every point has order r; without it the call is correct for ANY point of
+ * the curve.  out may be the same buffer as points, not a partial overlap.  n = 0 is DG16_OK; a null pointer with n > 0,
+ * n >= 2^30 or a group other than 1 or 2 is DG16_ERR_BAD_ARG, an unknown curve DG16_ERR_BAD_CURVE.  points, scalar, out:
+ * host pointers only.  Synchronous; runs on channel 0.  A large n runs in slices of the size
+ * dg16_ctx_set_points_mul_slice sets (default 2^16 points); the device copy of a slice, its table and its accumulators
+ * come from channel 0's workspace, the buffers dg16_points_mul uses at the same sizes (DG16_ERR_OOM leaves the context
+ * usable). */
+int dg16_points_scale(dg16_ctx *ctx, int curve, int group, const void *points_affine, const void *scalar /* 32 bytes */,
+                      size_t n, void *out_affine, int in_subgroup);
+
+/* One phase-2 contribution (snarkjs `zkey contribute`, the arithmetic of it): with d = delta,
+ *   l_out = d^-1 * l_query (n_l points)      h_out = d^-1 * h_query (n_h points)
+ *   fixed_out = fixed_points (the dg16_pk_create layout alpha_g1 | beta_g1 | delta_g1 | beta_g2 | delta_g2) with
+ *               delta_g1 and delta_g2 multiplied by d and the other three copied.
+ * Every other array of the key is unchanged by a contribution.  d^-1 is taken mod r on the host; both arrays go through
+ * dg16_points_scale's path with in_subgroup = 1: THE CALLER VOUCHES FOR THE KEY (every point on its curve and of order
+ * r), as for dg16_groth16_rerandomize.  Identity entries (zero bytes; a LibsnarkReduction key's last h_query entry is
+ * one) stay identities.  l_out, h_out, fixed_out may be the inputs.  n_l = 0 and n_h = 0 are legal.  All three curves; no
+ * pairing is involved.
+ * THE RANDOMNESS IS THE CALLER'S, as everywhere in this library: delta is 32 bytes, canonical, in [1, r) -- uniform, and
+ * forgotten by the caller afterwards; the call draws nothing and keeps nothing.  delta = 0 or delta >= r is
+ * DG16_ERR_BAD_ARG, checked before any work, as is a NULL pointer (l_query / h_query may be NULL with a zero count); an
+ * unknown curve is DG16_ERR_BAD_CURVE.  Host pointers only.  Synchronous; runs on channel 0. */
+int dg16_groth16_contribute(dg16_ctx *ctx, int curve, size_t n_l, size_t n_h, const void *l_query, const void *h_query,
+                            const void *fixed_points, const void *delta /* 32 bytes, canonical, in [1, r) */,
+                            void *l_out, void *h_out, void *fixed_out);
+
+/* Bits of dg16_phase2_report::failed. */
+#define DG16_P2_BAD_POINT 1u   /* a point with an unreduced coordinate, off its curve or outside the subgroup */
+#define DG16_P2_IDENTITY 2u    /* delta_g1 or delta_g2 of either key is O */
+#define DG16_P2_CHANGED 4u     /* an array a contribution does not touch differs between the keys */
+#define DG16_P2_DELTA 8u       /* delta_g1 and delta_g2 were not multiplied by the same d */
+#define DG16_P2_L 16u          /* l_query was not divided by that d */
+#define DG16_P2_H 32u          /* h_query was not divided by that d */
+typedef struct dg16_groth16_key {   /* the eight outputs of dg16_groth16_setup, host pointers */
+  const void *a_query, *b_g1_query, *b_g2_query, *h_query, *l_query, *fixed_points, *gamma_g2, *gamma_abc_g1;
+} dg16_groth16_key;
+typedef struct dg16_phase2_report {
+  uint32_t failed;        /* 0 = accepted; bits above */
+  uint32_t bad_array;     /* with DG16_P2_BAD_POINT: 0 l_query, 1 h_query, 2 delta_g1, 3 delta_g2 of `before`, 4 .. 7 of `after` */
+  uint64_t bad_index;     /* the smallest bad index in that array (the first array that has one) */
+  uint64_t n_bad_points;  /* over all eight arrays */
+} dg16_phase2_report;
+/* Is `after` the key `before` with delta replaced by d * delta for SOME d (snarkjs `zkey verify`, without the contribution chain)?  BN254
+ * and BLS12-381.  Both keys have the sizes of dg16_groth16_setup: l_query num_vars - num_inputs points, h_query
+ * domain_size.  With D1, D2, L, H the delta_g1, delta_g2, l_query, h_query of `before`, primes for `after`, and
+ * coefficients rho_k, a bit of report->failed is CLEAR when:
+ *   DG16_P2_BAD_POINT  dg16_points_check(subgroup = 1) finds nothing in L, H, D1, D2, L', H', D1', D2'
+ *   DG16_P2_IDENTITY   none of D1, D2, D1', D2' is the identity
+ *   DG16_P2_CHANGED    a_query, b_g1_query, b_g2_query, gamma_g2, gamma_abc_g1, and alpha_g1, beta_g1, beta_g2 of
+ *                      fixed_points, are byte-equal in both keys (a host memcmp)
+ *   DG16_P2_DELTA      e(D1', D2) = e(D1, D2')
+ *   DG16_P2_L          e(sum_k rho_k L'_k, D2') = e(sum_k rho_k L_k, D2)      (skipped for an empty l_query)
+ *   DG16_P2_H          the same with H over domain_size terms
+ * Membership runs first: with DG16_P2_BAD_POINT or DG16_P2_IDENTITY set the three pairing checks are skipped and
+ * their bits stay clear (the sums use the endomorphism split and the pairing assumes subgroup points).  The four sums
+ * are the library's MSM on the device; the three equalities are two Miller loops and one final exponentiation each, on
+ * the host.  The relation is transitive in d: a key any number of contributions after `before` is accepted.
+ * report->failed != 0 comes with DG16_OK: a rejected key is a result, not an error.
+ * THE COEFFICIENTS ARE THE CALLER'S, as in dg16_groth16_verify_aggregate: coeffs = max(num_vars - num_inputs,
+ * domain_size) x 16 bytes, each a little-endian unsigned 128-bit integer; each sum uses the first of them.  The
+ * contract: the rho_k are independent and uniform in [1, 2^128), and they are chosen AFTER both keys are fixed.  A key
+ * that fails an equation is then accepted with probability about 2^-128 per equation.  A zero coefficient is
+ * DG16_ERR_BAD_ARG, checked before any work.
+ * NOT CHECKED: a contributor's proof of knowledge of d and the hash chain of a ceremony transcript (snarkjs' `zkey
+ * verify` with the contribution chain) -- they need a hash-to-curve this library does not have.
+ * before, after, coeffs, report and every array: host pointers only.  Synchronous; runs on channel 0; the device copies
+ * are temporary (DG16_ERR_OOM leaves the context usable).  num_inputs = 0, num_inputs > num_vars, domain_size = 0, sizes
+ * of 2^28 or more, or a NULL pointer (l_query may be NULL when it is empty): DG16_ERR_BAD_ARG.  DG16_BLS12_377 (no pairing
+ * here): DG16_ERR_UNSUPPORTED.  An unknown curve: DG16_ERR_BAD_CURVE. */
+int dg16_groth16_verify_contribution(dg16_ctx *ctx, int curve, size_t num_inputs, size_t num_vars, size_t domain_size,
+                                     const dg16_groth16_key *before, const dg16_groth16_key *after,
+                                     const void *coeffs /* max(num_vars - num_inputs, domain_size) x 16 bytes */,
+                                     dg16_phase2_report *report);
+
 /* Duration in milliseconds of the dominant kernel(s) of the most recent call on `channel`
  * (HIP events recorded on the channel's stream); 0 if none.  which: 0 = whole call,
  * 1 = bucket accumulation (MSM) / butterfly passes (NTT); 2 = NOT a duration: the shader clock in MHz the chip held
