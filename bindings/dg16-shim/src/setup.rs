@@ -280,6 +280,60 @@ where
     Ok(out)
 }
 
+/// One party's share of a proving key, with the field names of the reference's `PackedProvingKeyShare`
+/// (groth16/src/proving_key.rs:26-33); a call site moves the five vectors into that struct.
+pub struct PackedKeyShare<E: Pairing> {
+    pub s: Vec<E::G1Affine>,
+    pub u: Vec<E::G1Affine>,
+    pub v: Vec<E::G2Affine>,
+    pub w: Vec<E::G1Affine>,
+    pub h: Vec<E::G1Affine>,
+}
+
+/// `PackedProvingKeyShare::pack_from_arkworks_proving_key` for ALL parties in one `dg16_pk_pack`: s <- a_query[1..],
+/// u <- h_query, w <- l_query, h <- b_g1_query[1..], v <- b_g2_query[1..], each cut into l-chunks (the last one padded
+/// with identities) and packed in the exponent.  Element i of the result is party i's share; the points are those the
+/// reference computes.  `in_subgroup`: a key's points have order r, so a caller who
+/// trusts its key sets it and the cofactor groups take the endomorphism split too.
+pub fn pack_proving_key<E, P1, P2>(pk: &ProvingKey<E>, pp: &crate::net::Pss, n_parties: usize, in_subgroup: bool)
+    -> Result<Vec<PackedKeyShare<E>>, Dg16Error>
+where
+    E: Pairing<G1Affine = Affine<P1>, G2Affine = Affine<P2>>,
+    P1: Dg16Config<ScalarField = E::ScalarField>,
+    P2: Dg16Config<ScalarField = E::ScalarField>,
+    P1::BaseField: FieldBytes,
+    P2::BaseField: FieldBytes,
+{
+    let (nv, m) = (pk.a_query.len(), pk.h_query.len());
+    if nv == 0 || pk.b_g1_query.len() != nv || pk.b_g2_query.len() != nv || pk.l_query.len() >= nv {
+        return Err(Dg16Error::Status(sys::DG16_ERR_BAD_ARG, "a proving key with queries of unequal lengths".into()));
+    }
+    let ni = nv - pk.l_query.len();
+    let (f1, f2) = (2 * <P1::BaseField as FieldBytes>::BYTES, 2 * <P2::BaseField as FieldBytes>::BYTES);
+    let chunks = |n: usize| unsafe { sys::dg16_pss_pack_chunks(pp.0, n) };
+    let (cq, cu, cw) = (chunks(nv - 1), chunks(m), chunks(nv - ni));
+    let (a, b1, b2) = (pack_affine(&pk.a_query), pack_affine(&pk.b_g1_query), pack_affine(&pk.b_g2_query));
+    let (hq, lq) = (pack_affine(&pk.h_query), pack_affine(&pk.l_query));
+    let (mut s, mut u, mut w) = (vec![0u8; n_parties * cq * f1], vec![0u8; n_parties * cu * f1], vec![0u8; n_parties * cw * f1]);
+    let (mut h, mut v) = (vec![0u8; n_parties * cq * f1], vec![0u8; n_parties * cq * f2]);
+    let out = sys::Dg16PkShares { s: s.as_mut_ptr().cast(), u: u.as_mut_ptr().cast(), v: v.as_mut_ptr().cast(),
+                                  w: w.as_mut_ptr().cast(), h: h.as_mut_ptr().cast() };
+    check(unsafe {
+        sys::dg16_pk_pack(CTX.0, pp.0, nv, ni, m, a.as_ptr().cast(), b1.as_ptr().cast(), b2.as_ptr().cast(),
+                          hq.as_ptr().cast(), lq.as_ptr().cast(), &out,
+                          if in_subgroup { 1 } else { 0 })
+    })?;
+    Ok((0..n_parties)
+        .map(|i| PackedKeyShare {
+            s: unpack_affine::<P1>(&s[i * cq * f1..(i + 1) * cq * f1]),
+            u: unpack_affine::<P1>(&u[i * cu * f1..(i + 1) * cu * f1]),
+            v: unpack_affine::<P2>(&v[i * cq * f2..(i + 1) * cq * f2]),
+            w: unpack_affine::<P1>(&w[i * cw * f1..(i + 1) * cw * f1]),
+            h: unpack_affine::<P1>(&h[i * cq * f1..(i + 1) * cq * f1]),
+        })
+        .collect())
+}
+
 struct PackedKey {
     arrays: [Vec<u8>; 8],
 }

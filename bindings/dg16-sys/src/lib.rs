@@ -181,6 +181,16 @@ pub struct Dg16Groth16Key {
     pub gamma_g2: *const c_void,
     pub gamma_abc_g1: *const c_void,
 }
+/// `dg16_pk_shares`: the five outputs of `dg16_pk_pack`, each party-major `[n][chunks]` affine points
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct Dg16PkShares {
+    pub s: *mut c_void,
+    pub u: *mut c_void,
+    pub v: *mut c_void,
+    pub w: *mut c_void,
+    pub h: *mut c_void,
+}
 /// `dg16_phase2_report`: what `dg16_groth16_verify_contribution` found (failed = 0: accepted; the DG16_P2_* bits below)
 #[repr(C)]
 #[derive(Clone, Copy, Debug, Default, PartialEq, Eq)]
@@ -379,6 +389,14 @@ extern "C" {
     pub fn dg16_pss_apply_exp(ctx: *mut Dg16Ctx, pp: *const Dg16Pss, group: c_int, which: c_int,
                               input: *const c_void, count: usize, out: *mut c_void, flags: c_uint,
                               channel: c_int) -> c_int;
+    // packexp_from_public over l-chunks for ALL parties at once, and a whole proving key (five of them); host pointers, synchronous,
+    // channel 0; byte-equal to dg16_pss_apply_exp(which = 0) on the identity-padded chunks, transposed to party-major
+    pub fn dg16_pss_pack_points(ctx: *mut Dg16Ctx, pp: *const Dg16Pss, group: c_int, points_affine: *const c_void,
+                                n_points: usize, shares: *mut c_void, in_subgroup: c_int) -> c_int;
+    pub fn dg16_pss_pack_chunks(pp: *const Dg16Pss, n_points: usize) -> usize;
+    pub fn dg16_pk_pack(ctx: *mut Dg16Ctx, pp: *const Dg16Pss, num_vars: usize, num_inputs: usize, domain_size: usize,
+                        a_query: *const c_void, b_g1_query: *const c_void, b_g2_query: *const c_void,
+                        h_query: *const c_void, l_query: *const c_void, out: *const Dg16PkShares, in_subgroup: c_int) -> c_int;
     // file formats, proof codec, verifier (host code of the library)
     pub fn dg16_io_error() -> *const c_char;
     pub fn dg16_r1cs_parse(data: *const c_void, bytes: usize, out: *mut *mut Dg16R1cs) -> c_int;

@@ -11,6 +11,7 @@
 // with the transposes folded into the indexing -- HBM-bound element-wise passes.
 #pragma once
 #include <condition_variable>
+#include <memory>
 
 #include "ctx.h"
 #include "types.h"
@@ -20,6 +21,10 @@ struct dg16_pss {
   int curve;
   unsigned l, t, n;
   void* mats;   // device: pack [n][l] | unpack [l][n] | unpack2 [l][n] | (canonical copies of the three) | v2sum [n] canonical
+  // dg16_pss_pack_points (pss_pack.h): the host schedule of the pack matrix per [group - 1][split], made on first use
+  // under sched_mu (parties are host threads) and kept for the handle's life
+  mutable std::mutex sched_mu;
+  mutable std::shared_ptr<const void> sched[2][2];
 };
 
 namespace dg16 {

@@ -66,6 +66,21 @@ class PackedSharingParams:
     def unpackexp(self, group, shares, degree2):
         return self._apply_exp(group, 2 if degree2 else 1, shares, self.n, self.l)
 
+    def pack_chunks(self, n_points):
+        return int(self.ctx.L.dg16_pss_pack_chunks(self.h, int(n_points)))
+
+    def pack_points(self, group, points, in_subgroup=False):
+        """`dg16_pss_pack_points`: the shares of ALL parties of a point vector cut into l-chunks (the last one padded
+        with identities), party-major: [n][chunks][limbs].  Byte-equal to packexp_from_public on the padded chunks,
+        transposed.  Host arrays; synchronous.  in_subgroup: the caller's word that every point has order r."""
+        nl = FQ_LIMBS64[self.curve] * 2 * (2 if group == 2 else 1)
+        pts = np.ascontiguousarray(points, dtype=np.uint64).reshape(-1, nl)
+        out = np.zeros((self.n, self.pack_chunks(pts.shape[0]), nl), dtype=np.uint64)
+        self.ctx._chk(self.ctx.L.dg16_pss_pack_points(self.ctx.h, self.h, group, _ptr(pts) if pts.shape[0] else None,
+                                                      pts.shape[0], _ptr(out) if pts.shape[0] else None,
+                                                      1 if in_subgroup else 0))
+        return out
+
 
 class LocalTestNet:
     """n parties in one process; party(i) is the handle the i-th caller passes to the d_* functions."""

@@ -3,6 +3,7 @@ from the dist-primitives mirror (dist.py).  Names follow the reference:
 
     qap_pss                            QAP::pss                               groth16/src/qap.rs:143-187
     pack_from_arkworks_proving_key     PackedProvingKeyShare::...             groth16/src/proving_key.rs:35-110
+    pack_proving_key                   the same through dg16_pk_pack (one call, all parties)
     pack_from_witness                  examples/sha256.rs:97-121
     A / B / C .compute                 groth16/src/prove.rs:21-136
     party_prove                        `dsha256`                              groth16/examples/sha256.rs:26-95
@@ -10,10 +11,12 @@ from the dist-primitives mirror (dist.py).  Names follow the reference:
 All arithmetic runs on the GPU through the C ABI; this file only moves numpy arrays between calls.
 """
 
+import ctypes
+
 import numpy as np
 
 from . import dist as D
-from .lib import FQ_LIMBS64, _ptr
+from .lib import FQ_LIMBS64, PkShares, _ptr
 
 
 def _bitrev_perm(n):
@@ -65,6 +68,31 @@ def pack_from_arkworks_proving_key(pp, pk):
     h = _packexp_chunks(pp, 1, pk["b_g1_query"][1:])
     v = _packexp_chunks(pp, 2, pk["b_g2_query"][1:])
     return [dict(s=s[i], u=u[i], w=w[i], h=h[i], v=v[i]) for i in range(pp.n)]
+
+
+def pack_proving_key(pp, pk, in_subgroup=False):
+    """pack_from_arkworks_proving_key through ONE `dg16_pk_pack`: the five queries are packed for all parties by the
+    schedule of the pack matrix (csrc/pss_pack.h) instead of five packexp_from_public calls.  Same result, byte for
+    byte: one dict (s, u, w, h, v) per party.  in_subgroup: a key's points have order r, so
+    a caller who trusts its key passes True and the cofactor groups are split too."""
+    curve, ctx = pp.curve, pp.ctx
+    nl1 = FQ_LIMBS64[curve] * 2
+    q = {k: np.ascontiguousarray(pk[k], dtype=np.uint64).reshape(-1, nl1 * (2 if k == "b_g2_query" else 1))
+         for k in ("a_query", "b_g1_query", "b_g2_query", "h_query", "l_query")}
+    num_vars, n_l, domain = q["a_query"].shape[0], q["l_query"].shape[0], q["h_query"].shape[0]
+    if q["b_g1_query"].shape[0] != num_vars or q["b_g2_query"].shape[0] != num_vars or not 0 <= n_l < num_vars:
+        raise ValueError("a_query, b_g1_query, b_g2_query must have num_vars points and l_query fewer")
+    out = {"s": np.zeros((pp.n, pp.pack_chunks(num_vars - 1), nl1), dtype=np.uint64),
+           "u": np.zeros((pp.n, pp.pack_chunks(domain), nl1), dtype=np.uint64),
+           "w": np.zeros((pp.n, pp.pack_chunks(n_l), nl1), dtype=np.uint64),
+           "h": np.zeros((pp.n, pp.pack_chunks(num_vars - 1), nl1), dtype=np.uint64),
+           "v": np.zeros((pp.n, pp.pack_chunks(num_vars - 1), 2 * nl1), dtype=np.uint64)}
+    ptr = lambda a: _ptr(a).value if a.size else None          # noqa: E731
+    shares = PkShares(**{k: ptr(v) for k, v in out.items()})
+    ctx._chk(ctx.L.dg16_pk_pack(ctx.h, pp.h, num_vars, num_vars - n_l, domain, ptr(q["a_query"]), ptr(q["b_g1_query"]),
+                                ptr(q["b_g2_query"]), ptr(q["h_query"]), ptr(q["l_query"]), ctypes.byref(shares),
+                                1 if in_subgroup else 0))
+    return [{k: np.ascontiguousarray(v[i]) for k, v in out.items()} for i in range(pp.n)]
 
 
 def _pt(curve, group, p):

@@ -75,6 +75,10 @@ class Groth16Key(ctypes.Structure):       # dg16_groth16_key
                                                "fixed_points", "gamma_g2", "gamma_abc_g1")]
 
 
+class PkShares(ctypes.Structure):         # dg16_pk_shares
+    _fields_ = [(n, ctypes.c_void_p) for n in ("s", "u", "v", "w", "h")]
+
+
 class Phase2ReportC(ctypes.Structure):    # dg16_phase2_report
     _fields_ = [("failed", ctypes.c_uint32), ("bad_array", ctypes.c_uint32), ("bad_index", ctypes.c_uint64),
                 ("n_bad_points", ctypes.c_uint64)]
@@ -292,6 +296,10 @@ def load():
     L.dg16_groth16_contribute.argtypes = [vp, i, sz, sz, vp, vp, vp, vp, vp, vp, vp]
     L.dg16_groth16_verify_contribution.argtypes = [vp, i, sz, sz, sz, ctypes.POINTER(Groth16Key),
                                                    ctypes.POINTER(Groth16Key), vp, ctypes.POINTER(Phase2ReportC)]
+    L.dg16_pss_pack_points.argtypes = [vp, vp, i, vp, sz, vp, i]
+    L.dg16_pss_pack_chunks.argtypes = [vp, sz]
+    L.dg16_pss_pack_chunks.restype = sz
+    L.dg16_pk_pack.argtypes = [vp, vp, sz, sz, sz, vp, vp, vp, vp, vp, ctypes.POINTER(PkShares), i]
     _lib = L
     return L
 
@@ -319,7 +327,7 @@ EXPORTED = ["dg16_ctx_create", "dg16_ctx_destroy", "dg16_last_error", "dg16_set_
             "dg16_points_mul", "dg16_ctx_set_points_mul_slice", "dg16_groth16_rerandomize",
             "dg16_groth16_setup_srs", "dg16_setup_srs_limits", "dg16_group_ntt", "dg16_srs_prepare",
             "dg16_points_check", "dg16_srs_verify", "dg16_points_scale", "dg16_groth16_contribute",
-            "dg16_groth16_verify_contribution"]
+            "dg16_groth16_verify_contribution", "dg16_pss_pack_points", "dg16_pss_pack_chunks", "dg16_pk_pack"]
 
 
 def _ptr(x):

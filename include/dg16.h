@@ -632,6 +632,44 @@ int dg16_pss_apply(dg16_ctx *ctx, const dg16_pss *pp, int which, const void *in,
 int dg16_pss_apply_exp(dg16_ctx *ctx, const dg16_pss *pp, int group, int which, const void *in,
                        size_t count, void *out, unsigned flags, int channel);
 
+/* packexp_from_public over l-chunks of a point vector, all parties at once (dist-primitives/src/dmsm/mod.rs:50-68 under
+ * groth16/src/proving_key.rs:67-81).  shares: party-major, [pp->n][chunks] affine points, chunks = ceil(n_points / l) =
+ * dg16_pss_pack_chunks(pp, n_points); share r of chunk e is sum_{c<l} M[r][c] * points[e * l + c] with M the pack matrix
+ * of pp and the last chunk padded with identities (arkworks' resize before the transform).
+ * THE CONTRACT: the result equals dg16_pss_apply_exp(which = 0) on the identity-padded chunks, transposed to party-major,
+ * BYTE FOR BYTE -- affine Montgomery coordinates are unique and the identity is zero bytes.  The path differs: the n * l
+ * multipliers are constants of (curve, l), so they are recoded once per handle (cached in pp; safe for concurrent host
+ * threads), an input point's odd multiples are tabulated once for all n parties, the l terms of a share run on one
+ * doubling chain, and the slice's results are converted with a batched inversion.
+ * points_affine and shares are HOST pointers, as for dg16_points_scale.  in_subgroup != 0 is the caller's word that
+ * every point has order r, which allows the endomorphism split for groups with a cofactor.  With in_subgroup = 0 the call
+ * is correct for ANY point of the curve and only BN254 G1 is split (dg16_points_mul's rule).
+ * Synchronous: the call runs on channel 0, is ordered behind the work enqueued on channel 0's stream, and the shares are
+ * complete on return.  A large input runs in slices whose outputs do not exceed what dg16_ctx_set_points_mul_slice sets
+ * (default 2^16), rounded to a multiple of 64 chunks; the device copy of a slice, its tables and its accumulators are
+ * channel 0's workspace, and DG16_ERR_OOM leaves the context usable.
+ * n_points = 0 is DG16_OK and writes nothing.  A NULL pointer with n_points > 0, a group other than 1 or 2,
+ * n_points >= 2^30, or a pp of another context: DG16_ERR_BAD_ARG, and nothing is written.  A partial overlap of input
+ * and output is the caller's error. */
+int dg16_pss_pack_points(dg16_ctx *ctx, const dg16_pss *pp, int group, const void *points_affine, size_t n_points,
+                         void *shares, int in_subgroup);
+size_t dg16_pss_pack_chunks(const dg16_pss *pp, size_t n_points);
+
+/* PackedProvingKeyShare::pack_from_arkworks_proving_key (proving_key.rs:35-110): s <- a_query[1..], u <- h_query,
+ * w <- l_query, h <- b_g1_query[1..], v <- b_g2_query[1..] (G2); each output party-major as above, five
+ * dg16_pss_pack_points under one call.  The arrays have the sizes of dg16_pk_create: a_query, b_g1_query, b_g2_query
+ * num_vars points, h_query domain_size, l_query num_vars - num_inputs.  num_vars = 1 makes the three [1..] queries
+ * empty, which is legal, and l_query (and out->w) may be NULL when num_vars == num_inputs; an empty query writes
+ * nothing.  Host pointers, in_subgroup, synchronisation and errors are those of dg16_pss_pack_points; num_inputs = 0,
+ * num_inputs > num_vars and sizes of 2^30 or more are DG16_ERR_BAD_ARG.  "Nothing is written" holds for these argument
+ * errors, which are all checked before any work.  The five queries are packed one after another in the order s, u, w, h,
+ * v, each complete before the next begins: a run-time failure in one of them (DG16_ERR_OOM, DG16_ERR_HIP) leaves the
+ * outputs of the earlier ones written and the later ones untouched. */
+typedef struct dg16_pk_shares { void *s, *u, *v, *w, *h; } dg16_pk_shares;
+int dg16_pk_pack(dg16_ctx *ctx, const dg16_pss *pp, size_t num_vars, size_t num_inputs, size_t domain_size,
+                 const void *a_query, const void *b_g1_query, const void *b_g2_query, const void *h_query,
+                 const void *l_query, const dg16_pk_shares *out, int in_subgroup);
+
 /* share: this party's share_len packed shares; share_len * l must equal 2^log_m (the reference's
  * debug assertion, dfft/mod.rs:31-37) else DG16_ERR_BAD_ARG; out: pad * share_len elements. */
 int dg16_d_fft(dg16_ctx *ctx, const dg16_pss *pp, const dg16_net *net, const void *share,
