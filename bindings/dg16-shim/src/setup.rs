@@ -250,6 +250,183 @@ where
     Ok(unpack_affine::<P>(&out))
 }
 
+fn scalar_bytes<F: PrimeField>(x: &F) -> Vec<u8> {
+    let mut b = x.into_bigint().to_bytes_le();
+    b.resize(32, 0);
+    b
+}
+
+/// `(first * ratio^(start + i)) * P_i` (`dg16_points_mul_series`): the scalars are a geometric series made on the
+/// device, nothing but `first` and `ratio` is uploaded.  `start + points.len()` must fit 64 bits.  `in_subgroup` as for
+/// `points_scale`.
+pub fn points_mul_series<P>(points: &[Affine<P>], first: &P::ScalarField, ratio: &P::ScalarField, start: u64,
+                            in_subgroup: bool) -> Result<Vec<Affine<P>>, Dg16Error>
+where
+    P: Dg16Config,
+    P::BaseField: FieldBytes,
+{
+    let raw = pack_affine(points);
+    let mut out = vec![0u8; raw.len()];
+    let (f, q) = (scalar_bytes(first), scalar_bytes(ratio));
+    check(unsafe {
+        sys::dg16_points_mul_series(CTX.0, P::CURVE, P::GROUP, raw.as_ptr().cast(), points.len(), f.as_ptr().cast(),
+                                    q.as_ptr().cast(), start, out.as_mut_ptr().cast(), if in_subgroup { 1 } else { 0 })
+    })?;
+    Ok(unpack_affine::<P>(&out))
+}
+
+/// The proof of knowledge of one phase-1 contribution: per secret x (tau, alpha, beta) `s_x G`, `s_x x G` and `x SP_x`.
+pub struct SrsContributionKey<E: Pairing> {
+    pub g1_s: [E::G1Affine; 3],
+    pub g1_sx: [E::G1Affine; 3],
+    pub g2_spx: [E::G2Affine; 3],
+}
+
+fn pack_contribution_key<E, P1, P2>(key: &SrsContributionKey<E>) -> Vec<u8>
+where
+    E: Pairing<G1Affine = Affine<P1>, G2Affine = Affine<P2>>,
+    P1: Dg16Config<ScalarField = E::ScalarField>,
+    P2: Dg16Config<ScalarField = E::ScalarField>,
+    P1::BaseField: FieldBytes,
+    P2::BaseField: FieldBytes,
+{
+    let mut raw = Vec::new();
+    for j in 0..3 {
+        raw.extend(pack_affine(&[key.g1_s[j], key.g1_sx[j]]));
+        raw.extend(pack_affine(&[key.g2_spx[j]]));
+    }
+    raw
+}
+
+/// One phase-1 contribution to a powers-of-tau transcript (`dg16_srs_contribute`): entry j of the four arrays times
+/// tau^j (and alpha, beta), `beta_g2` times beta.  `secrets` = [tau, alpha, beta], non-zero.  THE RANDOMNESS IS THE
+/// CALLER'S, and so is the challenge: with `proof` = (blinds [s_tau, s_alpha, s_beta], challenge points [SP_tau,
+/// SP_alpha, SP_beta]) the key is made too.  The caller vouches that the transcript's points have order r
+/// (`srs_verify` first).
+pub fn srs_contribute<E, P1, P2>(powers: &SrsPowers<E>, secrets: &[E::ScalarField; 3],
+                                 proof: Option<(&[E::ScalarField; 3], &[E::G2Affine; 3])>)
+    -> Result<(SrsPowers<E>, Option<SrsContributionKey<E>>), Dg16Error>
+where
+    E: Pairing<G1Affine = Affine<P1>, G2Affine = Affine<P2>>,
+    P1: Dg16Config<ScalarField = E::ScalarField>,
+    P2: Dg16Config<ScalarField = E::ScalarField>,
+    P1::BaseField: FieldBytes,
+    P2::BaseField: FieldBytes,
+{
+    let m = powers.tau_g2.len();
+    if !m.is_power_of_two() || powers.tau_g1.len() != 2 * m - 1 || powers.alpha_tau_g1.len() != m
+        || powers.beta_tau_g1.len() != m
+    {
+        return Err(Dg16Error::Status(sys::DG16_ERR_BAD_ARG, "powers: tau_g1 holds 2m - 1 points, the others m = 2^k".into()));
+    }
+    let log_m = m.trailing_zeros();
+    let (mut t1, mut t2) = (pack_affine(&powers.tau_g1), pack_affine(&powers.tau_g2));
+    let (mut at, mut bt, mut b2) =
+        (pack_affine(&powers.alpha_tau_g1), pack_affine(&powers.beta_tau_g1), pack_affine(&[powers.beta_g2]));
+    // every output is its input: the library allows it
+    let raw_in = sys::Dg16SrsPowers {
+        tau_g1: t1.as_ptr().cast(),
+        tau_g2: t2.as_ptr().cast(),
+        alpha_tau_g1: at.as_ptr().cast(),
+        beta_tau_g1: bt.as_ptr().cast(),
+        beta_g2: b2.as_ptr().cast(),
+    };
+    let raw_out = sys::Dg16SrsPowersOut {
+        tau_g1: t1.as_mut_ptr().cast(),
+        tau_g2: t2.as_mut_ptr().cast(),
+        alpha_tau_g1: at.as_mut_ptr().cast(),
+        beta_tau_g1: bt.as_mut_ptr().cast(),
+        beta_g2: b2.as_mut_ptr().cast(),
+    };
+    let sec: Vec<u8> = secrets.iter().flat_map(scalar_bytes).collect();
+    let (f1, f2) = (2 * <P1::BaseField as FieldBytes>::BYTES, 2 * <P2::BaseField as FieldBytes>::BYTES);
+    let mut key_raw = vec![0u8; 3 * (2 * f1 + f2)];
+    let (blinds, challenge): (Vec<u8>, Vec<u8>) = match proof {
+        Some((s, sp)) => (s.iter().flat_map(scalar_bytes).collect(), pack_affine(&sp[..])),
+        None => (Vec::new(), Vec::new()),
+    };
+    let opt = |v: &Vec<u8>| -> *const core::ffi::c_void {
+        if proof.is_some() { v.as_ptr().cast() } else { std::ptr::null() }
+    };
+    check(unsafe {
+        sys::dg16_srs_contribute(CTX.0, P1::CURVE, log_m, &raw_in, sec.as_ptr().cast(), opt(&blinds), opt(&challenge),
+                                 &raw_out, if proof.is_some() { key_raw.as_mut_ptr().cast() } else { std::ptr::null_mut() })
+    })?;
+    let out = SrsPowers::<E> {
+        tau_g1: unpack_affine::<P1>(&t1),
+        tau_g2: unpack_affine::<P2>(&t2),
+        alpha_tau_g1: unpack_affine::<P1>(&at),
+        beta_tau_g1: unpack_affine::<P1>(&bt),
+        beta_g2: unpack_affine::<P2>(&b2)[0],
+    };
+    let key = proof.map(|_| {
+        let part = |j: usize| &key_raw[j * (2 * f1 + f2)..(j + 1) * (2 * f1 + f2)];
+        let g1: Vec<Vec<Affine<P1>>> = (0..3).map(|j| unpack_affine::<P1>(&part(j)[..2 * f1])).collect();
+        let g2: Vec<Affine<P2>> = (0..3).map(|j| unpack_affine::<P2>(&part(j)[2 * f1..])[0]).collect();
+        SrsContributionKey::<E> {
+            g1_s: [g1[0][0], g1[1][0], g1[2][0]],
+            g1_sx: [g1[0][1], g1[1][1], g1[2][1]],
+            g2_spx: [g2[0], g2[1], g2[2]],
+        }
+    });
+    Ok((out, key))
+}
+
+/// Is `after` a contribution to `before` by whoever holds `key` under the challenge points
+/// (`dg16_srs_verify_contribution`)?  `after` is checked in full like `srs_verify` does (same `coeffs`: 2m - 2 integers
+/// in [1, 2^128) drawn AFTER `after` was fixed); of `before` only the head points are read.  `report.failed == 0`
+/// accepts; its bits are `sys::DG16_P1_*`.  A rejected contribution is `Ok` with the bits set.  Not checked: that the
+/// challenge is the hash of `before` -- the caller's protocol.
+pub fn srs_verify_contribution<E, P1, P2>(before: &SrsPowers<E>, after: &SrsPowers<E>, key: &SrsContributionKey<E>,
+                                          challenge: &[E::G2Affine; 3], coeffs: &[u128])
+    -> Result<sys::Dg16SrsContributionReport, Dg16Error>
+where
+    E: Pairing<G1Affine = Affine<P1>, G2Affine = Affine<P2>>,
+    P1: Dg16Config<ScalarField = E::ScalarField>,
+    P2: Dg16Config<ScalarField = E::ScalarField>,
+    P1::BaseField: FieldBytes,
+    P2::BaseField: FieldBytes,
+{
+    let m = after.tau_g2.len();
+    if !m.is_power_of_two() || m < 2 || after.tau_g1.len() != 2 * m - 1 || after.alpha_tau_g1.len() != m
+        || after.beta_tau_g1.len() != m || coeffs.len() != 2 * m - 2 || before.tau_g1.len() < 2 || before.tau_g2.len() < 2
+        || before.alpha_tau_g1.is_empty() || before.beta_tau_g1.is_empty()
+    {
+        return Err(Dg16Error::Status(sys::DG16_ERR_BAD_ARG,
+                                     "after: tau_g1 holds 2m - 1 points, the others m = 2^k >= 2; 2m - 2 coefficients; before: its heads".into()));
+    }
+    let log_m = m.trailing_zeros();
+    // of `before` the heads only
+    let (bt1, bt2) = (pack_affine(&before.tau_g1[..2]), pack_affine(&before.tau_g2[..2]));
+    let (bat, bbt, bb2) =
+        (pack_affine(&before.alpha_tau_g1[..1]), pack_affine(&before.beta_tau_g1[..1]), pack_affine(&[before.beta_g2]));
+    let raw_before = sys::Dg16SrsPowers {
+        tau_g1: bt1.as_ptr().cast(),
+        tau_g2: bt2.as_ptr().cast(),
+        alpha_tau_g1: bat.as_ptr().cast(),
+        beta_tau_g1: bbt.as_ptr().cast(),
+        beta_g2: bb2.as_ptr().cast(),
+    };
+    let (t1, t2) = (pack_affine(&after.tau_g1), pack_affine(&after.tau_g2));
+    let (at, bt, b2) = (pack_affine(&after.alpha_tau_g1), pack_affine(&after.beta_tau_g1), pack_affine(&[after.beta_g2]));
+    let raw_after = sys::Dg16SrsPowers {
+        tau_g1: t1.as_ptr().cast(),
+        tau_g2: t2.as_ptr().cast(),
+        alpha_tau_g1: at.as_ptr().cast(),
+        beta_tau_g1: bt.as_ptr().cast(),
+        beta_g2: b2.as_ptr().cast(),
+    };
+    let key_raw = pack_contribution_key::<E, P1, P2>(key);
+    let sp = pack_affine(&challenge[..]);
+    let rho: Vec<u8> = coeffs.iter().flat_map(|c| c.to_le_bytes()).collect();
+    let mut report = sys::Dg16SrsContributionReport::default();
+    check(unsafe {
+        sys::dg16_srs_verify_contribution(CTX.0, P1::CURVE, log_m, &raw_before, &raw_after, key_raw.as_ptr().cast(),
+                                          sp.as_ptr().cast(), rho.as_ptr().cast(), &mut report)
+    })?;
+    Ok(report)
+}
+
 /// One phase-2 contribution to `pk` (`dg16_groth16_contribute`): `delta_g1`, `delta_g2` times `delta`, `l_query` and
 /// `h_query` divided by it, everything else as it is.  THE RANDOMNESS IS THE CALLER'S: `delta` non-zero, uniform, and
 /// forgotten afterwards.  The caller vouches that the key's points have order r.

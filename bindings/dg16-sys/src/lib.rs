@@ -206,6 +206,37 @@ pub const DG16_P2_CHANGED: u32 = 4;
 pub const DG16_P2_DELTA: u32 = 8;
 pub const DG16_P2_L: u32 = 16;
 pub const DG16_P2_H: u32 = 32;
+/// `dg16_srs_powers_out`: the caller-allocated HOST buffers `dg16_srs_contribute` fills, sized like `dg16_srs_powers`
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct Dg16SrsPowersOut {
+    pub tau_g1: *mut c_void,
+    pub tau_g2: *mut c_void,
+    pub alpha_tau_g1: *mut c_void,
+    pub beta_tau_g1: *mut c_void,
+    pub beta_g2: *mut c_void,
+}
+/// `dg16_srs_contribution_report`: what `dg16_srs_verify_contribution` found (failed = 0: accepted; the DG16_P1_* bits
+/// below); `after` is `dg16_srs_verify`'s report of the new transcript
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default, PartialEq, Eq)]
+pub struct Dg16SrsContributionReport {
+    pub failed: u32,
+    pub n_bad_points: u32,
+    pub after: Dg16SrsReport,
+}
+pub const DG16_P1_AFTER: u32 = 1;
+pub const DG16_P1_BAD_POINT: u32 = 2;
+pub const DG16_P1_IDENTITY: u32 = 4;
+pub const DG16_P1_BASE: u32 = 8;
+pub const DG16_P1_KEY_TAU: u32 = 16;
+pub const DG16_P1_KEY_ALPHA: u32 = 32;
+pub const DG16_P1_KEY_BETA: u32 = 64;
+pub const DG16_P1_LINK_TAU_G1: u32 = 128;
+pub const DG16_P1_LINK_TAU_G2: u32 = 256;
+pub const DG16_P1_LINK_ALPHA: u32 = 512;
+pub const DG16_P1_LINK_BETA: u32 = 1024;
+pub const DG16_P1_LINK_BETA_G2: u32 = 2048;
 /// `dg16_srs_prepared`: the caller-allocated HOST buffers `dg16_srs_prepare` fills, laid out as the arrays of `dg16_srs`
 #[repr(C)]
 #[derive(Clone, Copy, Debug)]
@@ -324,6 +355,18 @@ extern "C" {
                                             domain_size: usize, before: *const Dg16Groth16Key,
                                             after: *const Dg16Groth16Key, coeffs: *const c_void,
                                             report: *mut Dg16Phase2Report) -> c_int;
+    // phase 1 of the key ceremony: a geometric series of scalars (made on the device) times n points, a contribution
+    // to a powers-of-tau transcript with its proof-of-knowledge key, and the check that one transcript is a
+    // contribution to another; host pointers only, synchronous, channel 0.  A rejected contribution is a result.
+    pub fn dg16_points_mul_series(ctx: *mut Dg16Ctx, curve: c_int, group: c_int, points_affine: *const c_void, n: usize,
+                                  first: *const c_void, ratio: *const c_void, start: u64, out_affine: *mut c_void,
+                                  in_subgroup: c_int) -> c_int;
+    pub fn dg16_srs_contribute(ctx: *mut Dg16Ctx, curve: c_int, log_m: c_uint, powers: *const Dg16SrsPowers,
+                               secrets: *const c_void, blinds: *const c_void, challenge_g2: *const c_void,
+                               out: *const Dg16SrsPowersOut, key_out: *mut c_void) -> c_int;
+    pub fn dg16_srs_verify_contribution(ctx: *mut Dg16Ctx, curve: c_int, log_m: c_uint, before: *const Dg16SrsPowers,
+                                        after: *const Dg16SrsPowers, key: *const c_void, challenge_g2: *const c_void,
+                                        coeffs: *const c_void, report: *mut Dg16SrsContributionReport) -> c_int;
     pub fn dg16_to_affine(ctx: *mut Dg16Ctx, curve: c_int, group: c_int, jac: *const c_void, out: *mut c_void,
                           n: usize, flags: c_uint, channel: c_int) -> c_int;
     // resident bases (a CRS is uploaded once; msm over its window tables)

@@ -22,4 +22,5 @@ from .keygen import generate_parameters_from_srs, srs_from_trapdoor, Srs  # noqa
 from .keygen import srs_from_powers, powers_from_trapdoor  # noqa: F401,E402
 from .keygen import verify_powers, SrsReport  # noqa: F401,E402
 from .keygen import contribute, verify_contribution, verify_parameters, Phase2Report  # noqa: F401,E402
+from .keygen import contribute_powers, verify_powers_contribution, Phase1Report  # noqa: F401,E402
 from .verify import PreparedVerifyingKey  # noqa: F401,E402

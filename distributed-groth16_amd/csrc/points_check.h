@@ -157,6 +157,34 @@ inline SrsShape srs_shape(unsigned log_m) {
   return {m, 2 * m - 1, m, 2 * m - 2, m - 1};
 }
 
+// ---- dg16_srs_verify_contribution: from the outcomes of the checks to the word ------------------------------------------
+// (the values of the DG16_P1_* bits of include/dg16.h; points_check.hip holds the static_asserts)
+constexpr uint32_t kP1After = 1u, kP1BadPoint = 2u, kP1Identity = 4u, kP1Base = 8u, kP1FirstRelation = 16u;
+constexpr int kP1Relations = 8;     // KEY_TAU, KEY_ALPHA, KEY_BETA, LINK_TAU_G1, LINK_TAU_G2, LINK_ALPHA, LINK_BETA, LINK_BETA_G2
+constexpr uint32_t kSrsBadPoint = 1u, kSrsIdentity = 2u;      // DG16_SRS_BAD_POINT, DG16_SRS_IDENTITY
+
+struct P1Outcomes {
+  uint32_t after_failed;            // dg16_srs_report::failed of `after`
+  bool bad_point, identity;         // among the key, the challenge and the heads of `before`
+  bool base_differs;                // tau_g1[0] or tau_g2[0]
+  bool relation_fails[kP1Relations];
+};
+// the pairings assume subgroup points that are not the identity: without that they are not run
+DG_HD bool p1_relations_skipped(uint32_t after_failed, bool bad_point, bool identity) {
+  return bad_point || identity || (after_failed & (kSrsBadPoint | kSrsIdentity)) != 0;
+}
+DG_HD uint32_t p1_decide(const P1Outcomes& o) {
+  uint32_t w = 0;
+  if (o.after_failed) w |= kP1After;
+  if (o.bad_point) w |= kP1BadPoint;
+  if (o.identity) w |= kP1Identity;
+  if (o.base_differs) w |= kP1Base;
+  if (!p1_relations_skipped(o.after_failed, o.bad_point, o.identity))
+    for (int j = 0; j < kP1Relations; j++)
+      if (o.relation_fails[j]) w |= kP1FirstRelation << j;
+  return w;
+}
+
 }  // namespace pchk
 }  // namespace dg16
 
@@ -224,6 +252,16 @@ template <> void phase2_verify_run<0>(Call&, size_t, size_t, size_t, const dg16_
                                       const void*, dg16_phase2_report*);
 template <> void phase2_verify_run<1>(Call&, size_t, size_t, size_t, const dg16_groth16_key*, const dg16_groth16_key*,
                                       const void*, dg16_phase2_report*);
+// the checks behind dg16_srs_verify_contribution (BN254, BLS12-381): srs_verify_run on `after`, membership of the key,
+// the challenge and the heads of `before`, and eight pairing equalities; argument checks are the caller's
+template <int CURVE>
+void phase1_verify_run(Call& k, unsigned log_m, const dg16_srs_powers* before, const dg16_srs_powers* after,
+                       const void* key, const void* challenge_g2, const void* coeffs,
+                       dg16_srs_contribution_report* report);
+template <> void phase1_verify_run<0>(Call&, unsigned, const dg16_srs_powers*, const dg16_srs_powers*, const void*,
+                                      const void*, const void*, dg16_srs_contribution_report*);
+template <> void phase1_verify_run<1>(Call&, unsigned, const dg16_srs_powers*, const dg16_srs_powers*, const void*,
+                                      const void*, const void*, dg16_srs_contribution_report*);
 
 }  // namespace dg16
 #endif

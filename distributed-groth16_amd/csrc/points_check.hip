@@ -1,11 +1,20 @@
-// C ABI of the membership check, of the transcript verifier and of the verifier of a phase-2 contribution
-// (include/dg16.h): dg16_points_check, dg16_srs_verify, dg16_groth16_verify_contribution.
+// C ABI of the membership check, of the transcript verifier and of the verifiers of a phase-2 and of a phase-1
+// contribution (include/dg16.h): dg16_points_check, dg16_srs_verify, dg16_groth16_verify_contribution,
+// dg16_srs_verify_contribution.
 // Argument checks, the device copies of the host arrays and the dispatch on the curve; the kernel and the transcript
-// checks live in the per-curve objects (points_check_curve.hip).  Both calls take host pointers only, run on channel 0
+// checks live in the per-curve objects (points_check_curve.hip).  All calls take host pointers only, run on channel 0
 // and are synchronous; their device buffers are freed on every path.
 #include "points_check.h"
 
 using namespace dg16;
+
+static_assert(pchk::kP1After == DG16_P1_AFTER && pchk::kP1BadPoint == DG16_P1_BAD_POINT &&
+                  pchk::kP1Identity == DG16_P1_IDENTITY && pchk::kP1Base == DG16_P1_BASE &&
+                  pchk::kP1FirstRelation == DG16_P1_KEY_TAU &&
+                  (pchk::kP1FirstRelation << (pchk::kP1Relations - 1)) == DG16_P1_LINK_BETA_G2,
+              "points_check.h and include/dg16.h disagree on the DG16_P1_* bits");
+static_assert(pchk::kSrsBadPoint == DG16_SRS_BAD_POINT && pchk::kSrsIdentity == DG16_SRS_IDENTITY,
+              "points_check.h and include/dg16.h disagree on the DG16_SRS_* bits");
 
 namespace {
 
@@ -122,6 +131,34 @@ int dg16_groth16_verify_contribution(dg16_ctx* ctx, int curve, size_t num_inputs
     Call k(ctx, 0);
     if (curve == DG16_BN254) phase2_verify_run<0>(k, num_inputs, num_vars, domain_size, before, after, coeffs, report);
     else phase2_verify_run<1>(k, num_inputs, num_vars, domain_size, before, after, coeffs, report);
+    k.finish();
+    DG_HIP(hipStreamSynchronize(k.s()));
+  });
+}
+
+int dg16_srs_verify_contribution(dg16_ctx* ctx, int curve, unsigned log_m, const dg16_srs_powers* before,
+                                 const dg16_srs_powers* after, const void* key, const void* challenge_g2,
+                                 const void* coeffs, dg16_srs_contribution_report* report) {
+  if (!ctx) return DG16_ERR_BAD_ARG;
+  return guarded(ctx, [&] {
+    DG_REQUIRE(curve >= 0 && curve <= 2, DG16_ERR_BAD_CURVE, "unknown curve id");
+    DG_REQUIRE(curve != DG16_BLS12_377, DG16_ERR_UNSUPPORTED, "contribution verification: BN254 and BLS12-381 only");
+    for (const dg16_srs_powers* pw : {before, after})
+      DG_REQUIRE(pw && pw->tau_g1 && pw->tau_g2 && pw->alpha_tau_g1 && pw->beta_tau_g1 && pw->beta_g2, DG16_ERR_BAD_ARG,
+                 "null powers");
+    DG_REQUIRE(key && challenge_g2 && coeffs && report, DG16_ERR_BAD_ARG, "null argument");
+    DG_REQUIRE(log_m >= 1 && log_m <= pchk::kMaxLogM && log_m + 1 <= kTwoAdicity[curve], DG16_ERR_BAD_ARG,
+               "need 1 <= log_m <= 26 and a domain of 2m inside the field's 2-adic subgroup");
+    const pchk::SrsShape sh = pchk::srs_shape(log_m);
+    const uint8_t* c = (const uint8_t*)coeffs;
+    for (size_t j = 0; j < sh.n_long; j++) {
+      uint8_t any = 0;
+      for (int b = 0; b < 16; b++) any |= c[16 * j + b];
+      DG_REQUIRE(any, DG16_ERR_BAD_ARG, "a coefficient is zero");
+    }
+    Call k(ctx, 0);
+    if (curve == DG16_BN254) phase1_verify_run<0>(k, log_m, before, after, key, challenge_g2, coeffs, report);
+    else phase1_verify_run<1>(k, log_m, before, after, key, challenge_g2, coeffs, report);
     k.finish();
     DG_HIP(hipStreamSynchronize(k.s()));
   });

@@ -1,6 +1,7 @@
 // Per-curve object of the membership check (points_check.h): points_check_kernel for G1 and G2 of curve DG_CURVE, and --
 // for the curves that have a pairing here (BN254, BLS12-381) -- the transcript checks of dg16_srs_verify and the checks
-// of a phase-2 contribution (dg16_groth16_verify_contribution), which run the same three stages.
+// of a phase-2 contribution (dg16_groth16_verify_contribution), which run the same three stages, and the checks of a
+// phase-1 contribution (dg16_srs_verify_contribution): the transcript checks on `after` and eight more equalities.
 //
 //   membership   the five arrays are copied to the device whole (the sums read them anyway) and checked with
 //                subgroup = 1, one result pair per array; the seven heads are compared with the identity on the host
@@ -237,6 +238,81 @@ void phase2_verify_run<DG_CURVE>(Call& k, size_t num_inputs, size_t num_vars, si
   if (!pairings_equal(d1[1], d2[0], d1[0], d2[1])) report->failed |= DG16_P2_DELTA;
   if (n_l && !pairings_equal(sums[2], d2[1], sums[0], d2[0])) report->failed |= DG16_P2_L;
   if (!pairings_equal(sums[3], d2[1], sums[1], d2[0])) report->failed |= DG16_P2_H;
+}
+
+// dg16_srs_verify_contribution: srs_verify_run on `after`, then membership of the 19 loose points (one launch per
+// group), the byte comparison of the bases and eight equalities; pchk::p1_decide makes the word
+template <>
+void phase1_verify_run<DG_CURVE>(Call& k, unsigned log_m, const dg16_srs_powers* before, const dg16_srs_powers* after,
+                                 const void* key, const void* challenge_g2, const void* coeffs,
+                                 dg16_srs_contribution_report* report) {
+  constexpr size_t g1b = sizeof(Affine<Fq>), g2b = sizeof(Affine<Fq2>);
+  memset(report, 0, sizeof *report);
+  srs_verify_run<DG_CURVE>(k, log_m, after, coeffs, &report->after);
+
+  struct Key {
+    Affine<Fq> g1_s, g1_sx;
+    Affine<Fq2> g2_spx;
+  } kx[3];      // tau, alpha, beta
+  static_assert(sizeof(Key) == 2 * g1b + g2b, "layout of a key");
+  Affine<Fq2> sp[3];
+  memcpy(kx, key, sizeof kx);
+  memcpy(sp, challenge_g2, sizeof sp);
+  // T0, T1, A0, B0 | U0, U1, beta_g2 of `before`; T0, T1, A0, B0 | U0, U1, beta_g2 of `after`
+  Affine<Fq> h1[2][4];
+  Affine<Fq2> h2[2][3];
+  const dg16_srs_powers* pw[2] = {before, after};
+  for (int s = 0; s < 2; s++) {
+    memcpy(&h1[s][0], pw[s]->tau_g1, 2 * g1b);
+    memcpy(&h1[s][2], pw[s]->alpha_tau_g1, g1b);
+    memcpy(&h1[s][3], pw[s]->beta_tau_g1, g1b);
+    memcpy(&h2[s][0], pw[s]->tau_g2, 2 * g2b);
+    memcpy(&h2[s][2], pw[s]->beta_g2, g2b);
+  }
+  // ---- membership: 6 + 4 points of G1, 3 + 3 + 3 of G2 ----
+  Affine<Fq> c1[10];
+  Affine<Fq2> c2[9];
+  for (int j = 0; j < 3; j++) {
+    c1[2 * j] = kx[j].g1_s;
+    c1[2 * j + 1] = kx[j].g1_sx;
+    c2[j] = kx[j].g2_spx;
+    c2[3 + j] = sp[j];
+    c2[6 + j] = h2[0][j];
+  }
+  for (int j = 0; j < 4; j++) c1[6 + j] = h1[0][j];
+  DeviceBuffers buf;
+  void* d1 = buf.get(sizeof c1);
+  void* d2 = buf.get(sizeof c2);
+  pchk::CheckResult res[2] = {{0ull, 10ull}, {0ull, 9ull}};
+  pchk::CheckResult* dres = (pchk::CheckResult*)buf.get(sizeof res);
+  DG_HIP(hipMemcpyAsync(d1, c1, sizeof c1, hipMemcpyHostToDevice, k.s()));
+  DG_HIP(hipMemcpyAsync(d2, c2, sizeof c2, hipMemcpyHostToDevice, k.s()));
+  DG_HIP(hipMemcpyAsync(dres, res, sizeof res, hipMemcpyHostToDevice, k.s()));
+  points_check_run<DG_CURVE>(k, 1, d1, 10, 0, 1, dres);
+  points_check_run<DG_CURVE>(k, 2, d2, 9, 0, 1, dres + 1);
+  DG_HIP(hipMemcpyAsync(res, dres, sizeof res, hipMemcpyDeviceToHost, k.s()));
+  DG_HIP(hipStreamSynchronize(k.s()));
+  report->n_bad_points = (uint32_t)(res[0].n_bad + res[1].n_bad);
+
+  pchk::P1Outcomes o = {};
+  o.after_failed = report->after.failed;
+  o.bad_point = report->n_bad_points != 0;
+  for (const Affine<Fq>& p : c1) o.identity |= all_zero(&p, g1b);
+  for (const Affine<Fq2>& p : c2) o.identity |= all_zero(&p, g2b);
+  o.base_differs = memcmp(&h1[0][0], &h1[1][0], g1b) != 0 || memcmp(&h2[0][0], &h2[1][0], g2b) != 0;
+  if (!pchk::p1_relations_skipped(o.after_failed, o.bad_point, o.identity)) {
+    // R(a, b; c, d): e(a, d) = e(b, c)
+    const auto fails = [](const Affine<Fq>& a, const Affine<Fq>& b, const Affine<Fq2>& c, const Affine<Fq2>& d) {
+      return !pairings_equal(a, d, b, c);
+    };
+    for (int j = 0; j < 3; j++) o.relation_fails[j] = fails(kx[j].g1_s, kx[j].g1_sx, sp[j], kx[j].g2_spx);
+    o.relation_fails[3] = fails(h1[0][1], h1[1][1], sp[0], kx[0].g2_spx);
+    o.relation_fails[4] = fails(kx[0].g1_s, kx[0].g1_sx, h2[0][1], h2[1][1]);
+    o.relation_fails[5] = fails(h1[0][2], h1[1][2], sp[1], kx[1].g2_spx);
+    o.relation_fails[6] = fails(h1[0][3], h1[1][3], sp[2], kx[2].g2_spx);
+    o.relation_fails[7] = fails(kx[2].g1_s, kx[2].g1_sx, h2[0][2], h2[1][2]);
+  }
+  report->failed = pchk::p1_decide(o);
 }
 #endif
 

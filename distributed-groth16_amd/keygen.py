@@ -16,6 +16,15 @@ csrc/group_ntt_curve.hip; snarkjs' `powersoftau prepare phase2`):
 
     srs = srs_from_powers(ctx, "bn254", log_m, tau_g1, tau_g2, alpha_tau_g1, beta_tau_g1, beta_g2)
 
+Before a transcript is trusted anybody may add randomness of their own to it, phase 1 of the ceremony: every power is
+multiplied by the matching power of a secret tau, alpha, beta (`dg16_srs_contribute`, csrc/points_series.h: the scalars
+are a geometric series made on the device), with a proof of knowledge per secret, and anybody can check that one
+transcript is such a contribution to another (`dg16_srs_verify_contribution`; snarkjs' `powersoftau contribute` and the
+contribution part of `powersoftau verify`, without the hashes, which stay with the caller):
+
+    powers2, key = contribute_powers(ctx, "bn254", log_m, powers, tau, alpha, beta, blinds=(s1, s2, s3), challenge=sp)
+    report = verify_powers_contribution(ctx, "bn254", log_m, powers, powers2, key, sp)      # report.accepted
+
 Such a key becomes one anybody may use through phase 2 of the ceremony -- every participant multiplies delta by a secret
 of their own (`dg16_groth16_contribute`, csrc/points_scale.h), and anybody can check the result against the circuit and
 the reference string (`dg16_groth16_verify_contribution`; snarkjs' `zkey contribute` and the key part of `zkey verify`):
@@ -348,6 +357,83 @@ def verify_powers(ctx, curve, log_m, tau_g1, tau_g2, alpha_tau_g1, beta_tau_g1, 
         u = np.ascontiguousarray(tau_g2, dtype=np.uint64).reshape(-1)
         match = bool(np.array_equal(t[:g1.size], g1) and np.array_equal(u[:g2.size], g2))
     return SrsReport(*rep, generators_match=match)
+
+
+def contribute_powers(ctx, curve, log_m, powers, tau, alpha, beta, blinds=None, challenge=None):
+    """One phase-1 contribution to a powers-of-tau transcript (`dg16_srs_contribute`; snarkjs' `powersoftau contribute`
+    without its hashes).  powers = (tau_g1, tau_g2, alpha_tau_g1, beta_tau_g1, beta_g2), the host arrays of
+    `srs_from_powers`; entry j of the first four is multiplied by tau^j (and by alpha, by beta), beta_g2 by beta.  THE
+    RANDOMNESS IS THE CALLER'S: tau, alpha, beta are ints in [1, r), uniform, and to be forgotten afterwards -- the
+    transcript is sound as long as ONE contributor did.  The caller vouches that the transcript's points have order r:
+    `verify_powers` first.  blinds = (s_tau, s_alpha, s_beta), ints in [1, r), and challenge = three G2 affine points
+    (uint64 [3][4 fq]; how they follow from the previous transcript is the caller's protocol) make the proof of
+    knowledge: key = s_x G | s_x x G | x SP_x per secret as one uint64 array, G = tau_g1[0]; without them no key is
+    made.  Returns (powers', key or None)."""
+    if curve not in FR_MODULUS:
+        raise ValueError("unknown curve %r" % (curve,))
+    r = FR_MODULUS[curve]
+    secrets_ = [int(x) for x in (tau, alpha, beta)]
+    if any(not 0 < x < r for x in secrets_):
+        raise ValueError("tau, alpha, beta must be non-zero and below r")
+    if log_m + 1 > TWO_ADICITY[curve] or log_m > 26:
+        raise ValueError("domain larger than the field's 2-adic subgroup")
+    if (blinds is None) != (challenge is None):
+        raise ValueError("blinds and challenge come together")
+    if blinds is not None:
+        blinds = [int(x) for x in blinds]
+        if len(blinds) != 3 or any(not 0 < x < r for x in blinds):
+            raise ValueError("blinds = (s_tau, s_alpha, s_beta), non-zero and below r")
+    return ctx.srs_contribute(curve, log_m, powers, secrets_, blinds=blinds, challenge_g2=challenge)
+
+
+class Phase1Report:
+    """What `verify_powers_contribution` found: `.accepted`, the word `.failed` (0 = accepted) and a name per bit of it,
+    the bits of dg16_srs_contribution_report in include/dg16.h.  `.after` is the SrsReport of the new transcript (bit
+    `after` is set when it is not clean); `.n_bad_points` counts the bad points among the key, the challenge and the
+    heads of the old transcript."""
+
+    AFTER, BAD_POINT, IDENTITY, BASE = 1, 2, 4, 8
+    KEY_TAU, KEY_ALPHA, KEY_BETA = 16, 32, 64
+    LINK_TAU_G1, LINK_TAU_G2, LINK_ALPHA, LINK_BETA, LINK_BETA_G2 = 128, 256, 512, 1024, 2048
+    NAMES = {1: "after", 2: "bad_point", 4: "identity", 8: "base", 16: "key_tau", 32: "key_alpha", 64: "key_beta",
+             128: "link_tau_g1", 256: "link_tau_g2", 512: "link_alpha", 1024: "link_beta", 2048: "link_beta_g2"}
+
+    def __init__(self, failed, n_bad_points=0, after=None):
+        self.failed = int(failed)
+        self.n_bad_points = int(n_bad_points)
+        self.after = after if isinstance(after, SrsReport) else SrsReport(*(after or (0,)))
+        for bit, name in self.NAMES.items():
+            if name != "after":
+                setattr(self, name, bool(self.failed & bit))
+
+    @property
+    def accepted(self):
+        return self.failed == 0
+
+    @property
+    def reasons(self):
+        return [name for bit, name in self.NAMES.items() if self.failed & bit]
+
+    def __repr__(self):
+        return "Phase1Report(accepted=%r, failed=%d %r)" % (self.accepted, self.failed, self.reasons)
+
+
+def verify_powers_contribution(ctx, curve, log_m, before, after, key, challenge, coeffs=None):
+    """Is the transcript `after` a contribution to `before` by whoever holds `key` (`dg16_srs_verify_contribution`; the
+    contribution part of snarkjs' `powersoftau verify`)?  before, after: five host arrays each, as for `verify_powers`;
+    `after` is checked in full the way `verify_powers` checks it, of `before` only the head points are read.  key: what
+    `contribute_powers` returned; challenge: the three G2 points the contributor was given.  The key must prove
+    knowledge of tau, alpha, beta under the challenge, and the heads of `after` must be those of `before` moved by
+    exactly these -- eight pairing equations.  coeffs: as for `verify_powers`, drawn AFTER `after` was fixed; None draws
+    them.  Not checked: that the challenge is the hash of `before` -- the caller's protocol.  BN254 and BLS12-381.
+    Returns a Phase1Report."""
+    if curve not in FR_MODULUS:
+        raise ValueError("unknown curve %r" % (curve,))
+    if coeffs is None:
+        from .verify import random_coefficients
+        coeffs = random_coefficients(2 * (1 << log_m) - 2)
+    failed, n_bad, rep = ctx.srs_verify_contribution(curve, log_m, before, after, key, challenge, coeffs)
+    return Phase1Report(failed, n_bad, rep)
 
 
 def generate_parameters_from_srs(ctx, curve, r1cs, srs, reduction="circom", in_subgroup=False):

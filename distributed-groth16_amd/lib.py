@@ -84,6 +84,14 @@ class Phase2ReportC(ctypes.Structure):    # dg16_phase2_report
                 ("n_bad_points", ctypes.c_uint64)]
 
 
+class SrsPowersOut(ctypes.Structure):     # dg16_srs_powers_out
+    _fields_ = [(n, ctypes.c_void_p) for n in ("tau_g1", "tau_g2", "alpha_tau_g1", "beta_tau_g1", "beta_g2")]
+
+
+class SrsContributionReportC(ctypes.Structure):    # dg16_srs_contribution_report
+    _fields_ = [("failed", ctypes.c_uint32), ("n_bad_points", ctypes.c_uint32), ("after", SrsReportC)]
+
+
 class PkInfo(ctypes.Structure):           # dg16_pk_info
     _fields_ = [("n_ab", ctypes.c_uint64), ("n_l", ctypes.c_uint64), ("n_h", ctypes.c_uint64),
                 ("c_ab", ctypes.c_uint32), ("c_l", ctypes.c_uint32), ("c_h", ctypes.c_uint32),
@@ -296,6 +304,10 @@ def load():
     L.dg16_groth16_contribute.argtypes = [vp, i, sz, sz, vp, vp, vp, vp, vp, vp, vp]
     L.dg16_groth16_verify_contribution.argtypes = [vp, i, sz, sz, sz, ctypes.POINTER(Groth16Key),
                                                    ctypes.POINTER(Groth16Key), vp, ctypes.POINTER(Phase2ReportC)]
+    L.dg16_points_mul_series.argtypes = [vp, i, i, vp, sz, vp, vp, ctypes.c_uint64, vp, i]
+    L.dg16_srs_contribute.argtypes = [vp, i, u, ctypes.POINTER(SrsPowers), vp, vp, vp, ctypes.POINTER(SrsPowersOut), vp]
+    L.dg16_srs_verify_contribution.argtypes = [vp, i, u, ctypes.POINTER(SrsPowers), ctypes.POINTER(SrsPowers), vp, vp, vp,
+                                               ctypes.POINTER(SrsContributionReportC)]
     L.dg16_pss_pack_points.argtypes = [vp, vp, i, vp, sz, vp, i]
     L.dg16_pss_pack_chunks.argtypes = [vp, sz]
     L.dg16_pss_pack_chunks.restype = sz
@@ -327,7 +339,8 @@ EXPORTED = ["dg16_ctx_create", "dg16_ctx_destroy", "dg16_last_error", "dg16_set_
             "dg16_points_mul", "dg16_ctx_set_points_mul_slice", "dg16_groth16_rerandomize",
             "dg16_groth16_setup_srs", "dg16_setup_srs_limits", "dg16_group_ntt", "dg16_srs_prepare",
             "dg16_points_check", "dg16_srs_verify", "dg16_points_scale", "dg16_groth16_contribute",
-            "dg16_groth16_verify_contribution", "dg16_pss_pack_points", "dg16_pss_pack_chunks", "dg16_pk_pack"]
+            "dg16_groth16_verify_contribution", "dg16_pss_pack_points", "dg16_pss_pack_chunks", "dg16_pk_pack",
+            "dg16_points_mul_series", "dg16_srs_contribute", "dg16_srs_verify_contribution"]
 
 
 def _ptr(x):
@@ -804,6 +817,104 @@ class Context:
                                                           ctypes.byref(ks[0]), ctypes.byref(ks[1]), _ptr(coeffs),
                                                           ctypes.byref(rep)))
         return rep.failed, rep.bad_array, rep.bad_index, rep.n_bad_points
+
+    def points_mul_series(self, curve, group, points, first, ratio, start=0, in_subgroup=False, out=None):
+        """out[i] = (first * ratio^(start + i) mod r) * points[i] (`dg16_points_mul_series`): first and ratio are ints in
+        [0, r) or 32 canonical bytes as uint64 [4] arrays, start an int with start + n < 2^64; the scalars are made on
+        the device.  points, in_subgroup and out are those of `points_scale`.  Synchronous."""
+        nl = FQ_LIMBS64[curve] * 2 * (2 if group == 2 else 1)
+        points = np.ascontiguousarray(points, dtype=np.uint64).reshape(-1, nl)
+        f, q = _scalar32(first), _scalar32(ratio)
+        start = int(start)
+        if not 0 <= start < 1 << 64:
+            raise ValueError("start is a 64-bit unsigned integer")
+        if out is None:
+            out = np.zeros_like(points)
+        elif not (isinstance(out, np.ndarray) and out.dtype == np.uint64 and out.flags.c_contiguous
+                  and out.size == points.size):
+            raise ValueError("out must be a contiguous uint64 array of the points' size")
+        n = points.shape[0]
+        self._chk(self.L.dg16_points_mul_series(self.h, CURVES[curve], group, _ptr(points) if n else None, n, _ptr(f),
+                                                _ptr(q), start, _ptr(out) if n else None, int(bool(in_subgroup))))
+        return out
+
+    @staticmethod
+    def _srs_powers(curve, log_m, arrays, which="powers", heads_only=False):
+        """The five arrays of a transcript as contiguous uint64 arrays of the right sizes (heads_only: at least the
+        head points `dg16_srs_verify_contribution` reads of `before`)."""
+        fq = FQ_LIMBS64[curve]
+        m = 1 << log_m
+        want = ((2 * m - 1, 2 * fq), (m, 4 * fq), (m, 2 * fq), (m, 2 * fq), (1, 4 * fq))
+        heads = (2, 2, 1, 1, 1)
+        arrays = tuple(arrays)
+        if len(arrays) != 5:
+            raise ValueError("%s = (tau_g1, tau_g2, alpha_tau_g1, beta_tau_g1, beta_g2)" % which)
+        ins = []
+        for name, arr, (rows, cols), head in zip(SrsPowers._fields_, arrays, want, heads):
+            arr = np.ascontiguousarray(arr, dtype=np.uint64)
+            if heads_only and arr.size % cols == 0 and head * cols <= arr.size <= rows * cols:
+                ins.append(arr.reshape(-1, cols))
+                continue
+            if arr.size != rows * cols:
+                raise ValueError("%s.%s must hold %d points" % (which, name[0], rows))
+            ins.append(arr.reshape(rows, cols))
+        return ins
+
+    def srs_contribute(self, curve, log_m, powers, secrets, blinds=None, challenge_g2=None, in_place=False):
+        """`dg16_srs_contribute`: one phase-1 contribution to the transcript powers = (tau_g1, tau_g2, alpha_tau_g1,
+        beta_tau_g1, beta_g2) (host arrays, the sizes of `srs_prepare`).  secrets = (tau, alpha, beta), ints in [1, r),
+        the CALLER's randomness.  With blinds = (s_tau, s_alpha, s_beta) and challenge_g2 (three G2 affine points, uint64
+        [3][4 fq]) the proof-of-knowledge key is made too: uint64 words of 3 x (G1 | G1 | G2).  The caller vouches that
+        the transcript's points have order r.  in_place=True writes into the given arrays (contiguous uint64 arrays).
+        Returns (the five new arrays, key or None).  Synchronous."""
+        fq = FQ_LIMBS64[curve]
+        ins = self._srs_powers(curve, log_m, powers)
+        if in_place and any(not isinstance(b, np.ndarray) or a.ctypes.data != b.ctypes.data for a, b in zip(ins, powers)):
+            raise ValueError("in_place needs contiguous uint64 arrays")
+        outs = ins if in_place else [np.zeros_like(a) for a in ins]      # (in place: views of the caller's arrays)
+        sec = np.concatenate([_scalar32(x) for x in secrets])
+        if sec.size != 12:
+            raise ValueError("secrets = (tau, alpha, beta)")
+        if (blinds is None) != (challenge_g2 is None):
+            raise ValueError("blinds and challenge_g2 come together")
+        bl = ch = key = None
+        if blinds is not None:
+            bl = np.concatenate([_scalar32(x) for x in blinds])
+            ch = np.ascontiguousarray(challenge_g2, dtype=np.uint64)
+            if bl.size != 12 or ch.size != 3 * 4 * fq:
+                raise ValueError("blinds = (s_tau, s_alpha, s_beta), challenge_g2 = three G2 points")
+            key = np.zeros(3 * (2 * 2 * fq + 4 * fq), dtype=np.uint64)
+        pw = SrsPowers(*[a.ctypes.data for a in ins])
+        po = SrsPowersOut(*[a.ctypes.data for a in outs])
+        self._chk(self.L.dg16_srs_contribute(self.h, CURVES[curve], log_m, ctypes.byref(pw), _ptr(sec), _ptr(bl), _ptr(ch),
+                                             ctypes.byref(po), _ptr(key)))
+        return tuple(powers) if in_place else tuple(outs), key
+
+    def srs_verify_contribution(self, curve, log_m, before, after, key, challenge_g2, coeffs):
+        """`dg16_srs_verify_contribution`: is the transcript `after` a contribution to `before` by whoever holds `key`
+        (the words `srs_contribute` returns) under the challenge points `challenge_g2`?  before / after: the five host
+        arrays of `srs_verify`; of `before` only the head points are read, and shorter arrays that hold them are
+        accepted.  coeffs: as for `srs_verify`, drawn AFTER `after` was fixed.  Returns (failed, n_bad_points, (failed,
+        bad_array, bad_index, n_bad_points) of `after`); failed = 0 accepts, its bits are the DG16_P1_* of the header
+        (`keygen.Phase1Report` names them).  Synchronous."""
+        fq = FQ_LIMBS64[curve]
+        m = 1 << log_m
+        b = self._srs_powers(curve, log_m, before, "before", heads_only=True)
+        a = self._srs_powers(curve, log_m, after, "after")
+        key = np.ascontiguousarray(key, dtype=np.uint64)
+        ch = np.ascontiguousarray(challenge_g2, dtype=np.uint64)
+        if key.size != 3 * 8 * fq or ch.size != 3 * 4 * fq:
+            raise ValueError("key = 3 x (G1 | G1 | G2), challenge_g2 = three G2 points")
+        coeffs = np.ascontiguousarray(coeffs, dtype=np.uint64)
+        if coeffs.size != (2 * m - 2) * 2:
+            raise ValueError("coeffs must hold %d 128-bit integers" % (2 * m - 2))
+        pb = SrsPowers(*[x.ctypes.data for x in b])
+        pa = SrsPowers(*[x.ctypes.data for x in a])
+        rep = SrsContributionReportC()
+        self._chk(self.L.dg16_srs_verify_contribution(self.h, CURVES[curve], log_m, ctypes.byref(pb), ctypes.byref(pa),
+                                                      _ptr(key), _ptr(ch), _ptr(coeffs), ctypes.byref(rep)))
+        r = rep.after
+        return rep.failed, rep.n_bad_points, (r.failed, r.bad_array, r.bad_index, r.n_bad_points)
 
     def to_affine(self, curve, group, jac, channel=0):
         jac = np.ascontiguousarray(jac, dtype=np.uint64)

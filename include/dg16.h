@@ -1002,6 +1002,106 @@ int dg16_groth16_verify_contribution(dg16_ctx *ctx, int curve, size_t num_inputs
                                      const void *coeffs /* max(num_vars - num_inputs, domain_size) x 16 bytes */,
                                      dg16_phase2_report *report);
 
+/* ---- Phase 1 of the key ceremony: a series of scalars times n points, a contribution to powers of tau, its check -----
+ * dg16_srs_verify checks a transcript and dg16_srs_prepare turns it into a reference string; these three make a
+ * contribution to one (snarkjs `powersoftau contribute`) and decide whether one transcript is a contribution to another
+ * (the contribution part of `powersoftau verify`).
+ *
+ * dg16_points_mul_series: out[i] = (first * ratio^(start + i) mod r) * points[i], i < n.  Layouts, curves and groups are
+ * those of dg16_points_mul, all six groups.  first, ratio: 32 bytes each, canonical little-endian integers in [0, r)
+ * (anything else is DG16_ERR_BAD_ARG, checked before any work).  ratio = 0 is legal: the term of exponent 0 is `first`
+ * and every other term is 0, the identity; first = 0 gives all identities; ratio = 1 gives what dg16_points_scale gives
+ * for `first`, byte for byte.  start + n must not exceed 2^64 - 1 (DG16_ERR_BAD_ARG).  The scalars are never on the host:
+ * a kernel writes each slice's terms, in Montgomery form, into the buffer dg16_points_mul's kernel reads -- a lane raises
+ * ratio to the first of its 16 consecutive exponents, a full 64-bit number, and multiplies on.
+ * in_subgroup has the meaning it has for dg16_points_scale: without it the call is correct for ANY point of the curve.
+ * out may be the same buffer as points, not a partial overlap.  n = 0 is DG16_OK; a null pointer with n > 0, n >= 2^30 or
+ * a group other than 1 or 2 is DG16_ERR_BAD_ARG, an unknown curve DG16_ERR_BAD_CURVE.  points, first, ratio, out: host
+ * pointers only.  Synchronous; runs on channel 0.  A large n runs in slices of the size dg16_ctx_set_points_mul_slice
+ * sets (default 2^16 points); the device copy of a slice and its scalars come from channel 0's workspace (DG16_ERR_OOM
+ * leaves the context usable). */
+int dg16_points_mul_series(dg16_ctx *ctx, int curve, int group, const void *points_affine, size_t n,
+                           const void *first /* 32 bytes */, const void *ratio /* 32 bytes */, uint64_t start,
+                           void *out_affine, int in_subgroup);
+
+/* Where dg16_srs_contribute writes: caller-allocated host buffers with the sizes of dg16_srs_powers. */
+typedef struct dg16_srs_powers_out {
+  void *tau_g1, *tau_g2, *alpha_tau_g1, *beta_tau_g1, *beta_g2;
+} dg16_srs_powers_out;
+/* One phase-1 contribution (snarkjs `powersoftau contribute`, the arithmetic of it).  With m = 2^log_m:
+ *   tau_g1'[j] = tau^j tau_g1[j] (j < 2m - 1)            tau_g2'[j] = tau^j tau_g2[j] (j < m)
+ *   alpha_tau_g1'[j] = alpha tau^j alpha_tau_g1[j]       beta_tau_g1'[j] = beta tau^j beta_tau_g1[j] (j < m)
+ *   beta_g2' = beta beta_g2
+ * The four arrays are four runs of dg16_points_mul_series' path with in_subgroup = 1, beta_g2 goes through
+ * dg16_points_scale's: THE CALLER VOUCHES FOR THE TRANSCRIPT (every point on its curve and of order r), as for
+ * dg16_groth16_contribute -- run dg16_srs_verify first.  Every output array may be its input array.  All three curves;
+ * no pairing is involved.  The log_m limits are dg16_srs_prepare's.
+ * secrets: tau | alpha | beta, 3 x 32 bytes, canonical, each in [1, r).  THE RANDOMNESS IS THE CALLER'S, and so is the
+ * challenge: the library draws nothing, hashes nothing and keeps nothing.
+ * The key is a proof of knowledge per secret.  blinds: s_tau | s_alpha | s_beta in the same form; challenge_g2: SP_tau |
+ * SP_alpha | SP_beta, three G2 affine points (how they are derived from the previous transcript is the caller's
+ * protocol; snarkjs hashes a challenge to G2).  With G = powers->tau_g1[0] and x over tau, alpha, beta, key_out holds
+ * s_x G | s_x x G | x SP_x for each x in that order: 6 G1 and 3 G2 affine points, each x's two G1 points followed by its
+ * G2 point.  blinds, challenge_g2 and key_out are all three NULL (no key is made) or none of them is; a partial triple is
+ * DG16_ERR_BAD_ARG.  A secret or blind that is zero or not below r is DG16_ERR_BAD_ARG, checked before any work, as is a
+ * NULL pointer; an unknown curve is DG16_ERR_BAD_CURVE.  Host pointers only.  Synchronous; runs on channel 0.
+ * Not here: the contribution hashes and the hash-to-G2 of a challenge, a .ptau reader, device-pointer forms. */
+int dg16_srs_contribute(dg16_ctx *ctx, int curve, unsigned log_m, const dg16_srs_powers *powers,
+                        const void *secrets /* tau | alpha | beta, 3 x 32 bytes */,
+                        const void *blinds /* s_tau | s_alpha | s_beta; NULL: no key is made */,
+                        const void *challenge_g2 /* SP_tau | SP_alpha | SP_beta; NULL with blinds */,
+                        const dg16_srs_powers_out *out, void *key_out /* NULL with blinds */);
+
+/* Bits of dg16_srs_contribution_report::failed. */
+#define DG16_P1_AFTER 1u          /* `after` is not a transcript: report->after says why */
+#define DG16_P1_BAD_POINT 2u      /* a key point, a challenge point or a head of `before` is unreduced, off its curve or outside the subgroup */
+#define DG16_P1_IDENTITY 4u       /* one of those points is O */
+#define DG16_P1_BASE 8u           /* tau_g1[0] or tau_g2[0] differs between the transcripts */
+#define DG16_P1_KEY_TAU 16u       /* the tau key is not a proof of knowledge under SP_tau */
+#define DG16_P1_KEY_ALPHA 32u     /* the alpha key, SP_alpha */
+#define DG16_P1_KEY_BETA 64u      /* the beta key, SP_beta */
+#define DG16_P1_LINK_TAU_G1 128u  /* tau_g1[1] did not move by the tau of the key */
+#define DG16_P1_LINK_TAU_G2 256u  /* tau_g2[1] did not */
+#define DG16_P1_LINK_ALPHA 512u   /* alpha_tau_g1[0] did not move by the alpha of the key */
+#define DG16_P1_LINK_BETA 1024u   /* beta_tau_g1[0] did not move by the beta of the key */
+#define DG16_P1_LINK_BETA_G2 2048u /* beta_g2 did not */
+typedef struct dg16_srs_contribution_report {
+  uint32_t failed;        /* 0 = accepted; bits above */
+  uint32_t n_bad_points;  /* with DG16_P1_BAD_POINT: how many of the 19 points (9 key, 3 challenge, 7 heads) */
+  dg16_srs_report after;  /* what dg16_srs_verify says about `after` */
+} dg16_srs_contribution_report;
+/* Is `after` a contribution to `before` by whoever holds this key (the contribution part of snarkjs `powersoftau
+ * verify`)?  BN254 and BLS12-381.  key: the 9 points dg16_srs_contribute writes; challenge_g2: the three points the
+ * contributor was given.  The call reads `after` in full (dg16_srs_verify's checks, same coeffs) and of `before` only
+ * the heads T0 = tau_g1[0], T1 = tau_g1[1], U0 = tau_g2[0], U1 = tau_g2[1], A0 = alpha_tau_g1[0], B0 = beta_tau_g1[0]
+ * and beta_g2 (the other entries of `before` may be absent: each array needs its first two, or its first one, point).
+ * Write R(a, b; c, d) for e(a, d) = e(b, c), and key.x = (g1_s, g1_sx, g2_spx).  A bit of report->failed is CLEAR when:
+ *   DG16_P1_AFTER         report->after.failed == 0
+ *   DG16_P1_BAD_POINT     dg16_points_check(subgroup = 1) finds nothing among the 9 key points, the 3 challenge points
+ *                         and the 7 heads of `before`
+ *   DG16_P1_IDENTITY      none of those 19 points is the identity
+ *   DG16_P1_BASE          tau_g1[0] and tau_g2[0] of `after` equal those of `before`, byte for byte
+ *   DG16_P1_KEY_TAU       R(key.tau.g1_s, key.tau.g1_sx; SP_tau, key.tau.g2_spx)        (KEY_ALPHA, KEY_BETA alike)
+ *   DG16_P1_LINK_TAU_G1   R(before.T1, after.T1; SP_tau, key.tau.g2_spx)
+ *   DG16_P1_LINK_TAU_G2   R(key.tau.g1_s, key.tau.g1_sx; before.U1, after.U1)
+ *   DG16_P1_LINK_ALPHA    R(before.A0, after.A0; SP_alpha, key.alpha.g2_spx)
+ *   DG16_P1_LINK_BETA     R(before.B0, after.B0; SP_beta, key.beta.g2_spx)
+ *   DG16_P1_LINK_BETA_G2  R(key.beta.g1_s, key.beta.g1_sx; before.beta_g2, after.beta_g2)
+ * The eight equalities are two Miller loops and one final exponentiation each, on the host.  They are skipped, and their
+ * bits stay clear, with DG16_P1_BAD_POINT or DG16_P1_IDENTITY set here or DG16_SRS_BAD_POINT or DG16_SRS_IDENTITY set in
+ * report->after: the pairing assumes subgroup points (dg16_srs_verify's rule).  Together with a clean report->after the
+ * links at the heads fix every entry: `after` is then a progression in ONE tau', alpha', beta', and the heads say which.
+ * report->failed != 0 comes with DG16_OK: a bad contribution is a result, not an error.
+ * coeffs: (2m - 2) x 16 bytes under dg16_srs_verify's contract; a zero coefficient is DG16_ERR_BAD_ARG, checked before
+ * any work, as are a NULL pointer and a log_m outside dg16_srs_verify's range.  DG16_BLS12_377 (no pairing here):
+ * DG16_ERR_UNSUPPORTED.  An unknown curve: DG16_ERR_BAD_CURVE.  Host pointers only.  Synchronous; runs on channel 0.
+ * NOT CHECKED: that challenge_g2 is the hash of the previous transcript -- the caller's protocol. */
+int dg16_srs_verify_contribution(dg16_ctx *ctx, int curve, unsigned log_m, const dg16_srs_powers *before,
+                                 const dg16_srs_powers *after, const void *key /* 3 x (G1 | G1 | G2) */,
+                                 const void *challenge_g2 /* 3 G2 points */,
+                                 const void *coeffs /* (2m - 2) x 16 bytes, as dg16_srs_verify */,
+                                 dg16_srs_contribution_report *report);
+
 /* Duration in milliseconds of the dominant kernel(s) of the most recent call on `channel`
  * (HIP events recorded on the channel's stream); 0 if none.  which: 0 = whole call,
  * 1 = bucket accumulation (MSM) / butterfly passes (NTT); 2 = NOT a duration: the shader clock in MHz the chip held
