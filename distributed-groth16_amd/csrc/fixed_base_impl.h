@@ -165,6 +165,18 @@ __global__ void __launch_bounds__(64) fb_affine_kernel(const XYZZ<F>* __restrict
   }
 }
 
+// out[i] = affine(acc[i]), i < cnt, on the call's stream; pref: cnt elements of scratch.  One inversion per lane: 32
+// points per lane once there are enough lanes (2^13) to fill the chip without it
+template <class F>
+void fb_to_affine(Call& k, const XYZZ<F>* acc, F* pref, size_t cnt, Affine<F>* out) {
+  unsigned per_lane = (unsigned)(cnt >> 13);
+  per_lane = per_lane < 1 ? 1 : per_lane > 32 ? 32 : per_lane;
+  const size_t lanes = (cnt + per_lane - 1) / per_lane;
+  hipLaunchKernelGGL(fb_affine_kernel<F>, dim3((unsigned)((lanes + 63) / 64)), dim3(64), 0, k.s(), acc, pref, cnt, lanes,
+                     per_lane, out);
+  DG_HIP(hipGetLastError());
+}
+
 // scalars_dev, out_dev: device pointers; base_host: one affine point on the host or NULL for the standard generator.
 // Workspace slots of the channel: 3 (base + window bases), 12 (table), 13 (accumulators), 14 (prefix products).
 template <class F, class C, class Fr, int BITS>
@@ -192,15 +204,10 @@ void fixed_base_typed(Call& k, const void* base_host, const void* scalars_dev, s
     const size_t cnt = n - lo < kFbBatch ? n - lo : kFbBatch;
     hipLaunchKernelGGL((fb_mul_kernel<F, Fr>), dim3((unsigned)((cnt + 63) / 64)), dim3(64), 0, k.s(), table,
                        (const Fr*)scalars_dev + lo, cnt, (int)mont, c, nwin, acc);
-    // one inversion per lane: 32 points per lane once there are enough lanes to fill the chip without it
-    unsigned per_lane = (unsigned)(cnt >> 13);
-    per_lane = per_lane < 1 ? 1 : per_lane > 32 ? 32 : per_lane;
-    const size_t lanes = (cnt + per_lane - 1) / per_lane;
-    hipLaunchKernelGGL(fb_affine_kernel<F>, dim3((unsigned)((lanes + 63) / 64)), dim3(64), 0, k.s(), acc, pref, cnt,
-                       lanes, per_lane, (Affine<F>*)out_dev + lo);
+    DG_HIP(hipGetLastError());
+    fb_to_affine(k, acc, pref, cnt, (Affine<F>*)out_dev + lo);
   }
   k.end_dominant();
-  DG_HIP(hipGetLastError());
 }
 
 }  // namespace dg16

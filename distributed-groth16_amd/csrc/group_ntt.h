@@ -12,7 +12,7 @@
 //   launches   e = 0 exactly for the lanes j < n / 2^s: they come FIRST in every stage and run in an add/sub launch of
 //              their own (all of stage 1); the lanes from n / 2^s on multiply.  A wave never holds both kinds.
 //   slices     each of the two lane ranges of a stage is cut into runs of at most `slice` lanes
-//              (dg16_ctx_set_points_mul_slice, default 2^16 as in points_mul.h): the table of a slice is 8 XYZZ per
+//              (dg16_ctx_set_points_mul_slice; slices.h: slice_lanes, launch_stride): the table of a slice is 8 XYZZ per
 //              lane, whatever n is.  The XYZZ results of a stage lie as the destination does (lane j's at j and
 //              j + n / 2), so ONE launch of fixed_base_impl.h's batched inversion converts a whole stage in place.
 //   butterfly  t = w b through pmul::product_split (every input is in the order-r subgroup by the call's contract, so the
@@ -33,7 +33,6 @@ namespace dg16 {
 namespace gntt {
 
 constexpr unsigned kMaxLog = 27;                     // dg16_ntt's limit
-constexpr size_t kSliceDefault = (size_t)1 << 16;    // points_mul.h's kSliceDefault (asserted in its device part)
 
 enum Launch : int { kAddSub = 0, kMul = 1 };
 
@@ -69,17 +68,14 @@ DG_HD Pair pair_of(unsigned log_n, unsigned s, size_t j) {
 DG_HD size_t trivial_lanes(unsigned log_n, unsigned s) { return (size_t)1 << (log_n - s); }
 DG_HD Launch launch_of(unsigned log_n, unsigned s, size_t j) { return j < trivial_lanes(log_n, s) ? kAddSub : kMul; }
 
-// 0 = default; rounded up to whole waves as dg16_points_mul does
-inline size_t slice_lanes(size_t ctx_slice) {
-  const size_t s = ctx_slice ? ctx_slice : kSliceDefault;
-  return (s + 63) / 64 * 64;
-}
+using dg16::slice_lanes;      // (slices.h's, under the names the plan has been tested by)
+using dg16::launch_stride;
 
 struct Slice {      // lanes [lo, lo + cnt) of one stage, all of one kind
   Launch kind;
   size_t lo, cnt;
 };
-// the launches of stage s in order; slice from slice_lanes()
+// the launches of stage s in order; slice from slices.h's slice_lanes()
 inline std::vector<Slice> stage_slices(unsigned log_n, unsigned s, size_t slice) {
   std::vector<Slice> out;
   const size_t half = (size_t)1 << (log_n - 1), triv = trivial_lanes(log_n, s);
@@ -93,8 +89,6 @@ inline std::vector<Slice> scale_slices(size_t n, size_t slice) {
   for (size_t lo = 0; lo < n; lo += slice) out.push_back(Slice{kMul, lo, n - lo < slice ? n - lo : slice});
   return out;
 }
-// lanes of the largest launch of a transform: what the workspace of a call is sized for
-inline size_t launch_stride(size_t lanes, size_t slice) { return lanes < slice ? (lanes + 63) / 64 * 64 : slice; }
 DG_HD size_t forward_products(unsigned log_n) {
   return log_n ? ((size_t)log_n << (log_n - 1)) - (((size_t)1 << log_n) - 1) : 0;
 }
@@ -155,9 +149,6 @@ struct PointOps {
 #if defined(__HIPCC__)
 // ---- device side ----------------------------------------------------------------------------------------------------------
 namespace dg16 {
-namespace gntt {
-static_assert(kSliceDefault == pmul::kSliceDefault, "one default slice for dg16_points_mul and dg16_group_ntt");
-}
 
 // All pointers are device buffers of affine points of `group`.  (defined in the per-curve objects group_ntt_<curve>.o)
 //

@@ -98,8 +98,8 @@ struct Work {
   F* pref = nullptr;
   size_t stride = 0, slice = 0;
   Work(Call& k, size_t lanes, size_t points, bool tables) {
-    slice = gntt::slice_lanes(k.ctx->points_mul_slice);
-    stride = gntt::launch_stride(lanes, slice);
+    slice = slice_lanes(k.ctx->points_mul_slice);
+    stride = launch_stride(lanes, slice);
     constexpr size_t W = sizeof(XYZZ<F>) / 4;
     if (tables) table = (uint32_t*)ws(k.c, 20, (size_t)pmul::kTable * W * stride * 4);
     DG_HIP(hipMalloc((void**)&acc, points * sizeof(XYZZ<F>)));
@@ -113,17 +113,6 @@ struct Work {
   Work& operator=(const Work&) = delete;
 };
 
-// out[i] = affine(acc[i]), i < cnt
-template <class F>
-void to_affine(Call& k, const Work<F>& w, size_t cnt, Affine<F>* out) {
-  unsigned per_lane = (unsigned)(cnt >> 13);
-  per_lane = per_lane < 1 ? 1 : per_lane > 32 ? 32 : per_lane;
-  const size_t lanes = (cnt + per_lane - 1) / per_lane;
-  hipLaunchKernelGGL(fb_affine_kernel<F>, dim3((unsigned)((lanes + 63) / 64)), dim3(64), 0, k.s(),
-                     (const XYZZ<F>*)w.acc, w.pref, cnt, lanes, per_lane, out);
-  DG_HIP(hipGetLastError());
-}
-
 // one pass of products: out[j] = w^(e_step j) * scale * src[j], j < n
 template <class F>
 void scale_pass(Call& k, const Work<F>& w, const Affine<F>* src, size_t n, const TwiddleSet& ts, size_t e_step,
@@ -134,7 +123,7 @@ void scale_pass(Call& k, const Work<F>& w, const Affine<F>* src, size_t n, const
                        w.stride, (size_t)0, w.acc + sl.lo);
     DG_HIP(hipGetLastError());
   }
-  to_affine<F>(k, w, n, out);
+  fb_to_affine(k, w.acc, w.pref, n, out);
 }
 
 template <class F>
@@ -158,7 +147,7 @@ void* transform(Call& k, void* xv, void* yv, unsigned log_n, int inverse, bool s
                            half, w.acc + sl.lo);
       DG_HIP(hipGetLastError());
     }
-    to_affine<F>(k, w, n, dst);       // results j and n / 2 + j are the destination's positions
+    fb_to_affine(k, w.acc, w.pref, n, dst);       // results j and n / 2 + j are the destination's positions
     Affine<F>* t = src;
     src = dst;
     dst = t;
@@ -187,7 +176,7 @@ void group_diff_run<DG_CURVE>(Call& k, const void* src, size_t a_off, size_t b_o
                        (const Affine<Fq>*)src, 0u, 0u, sl.lo, sl.cnt, a_off, b_off, (size_t)0, w.acc + sl.lo);
     DG_HIP(hipGetLastError());
   }
-  to_affine<Fq>(k, w, n, (Affine<Fq>*)out);
+  fb_to_affine(k, w.acc, w.pref, n, (Affine<Fq>*)out);
 }
 
 template <>

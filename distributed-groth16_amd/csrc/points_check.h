@@ -24,6 +24,7 @@
 // address and undefined-behaviour sanitizers against plain-Python decisions.
 #pragma once
 #include "ec29.h"
+#include "slices.h"
 #include "types.h"
 
 namespace dg16 {
@@ -195,8 +196,6 @@ DG_HD uint32_t p1_decide(const P1Outcomes& o) {
 
 namespace dg16 {
 namespace pchk {
-
-constexpr size_t kSliceDefault = (size_t)1 << 16;   // points per launch and per temporary device copy
 
 struct CheckResult {              // device words of one call: bad points, the smallest bad index (n when none)
   unsigned long long n_bad;

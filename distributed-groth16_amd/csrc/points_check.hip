@@ -54,8 +54,7 @@ int dg16_points_check(dg16_ctx* ctx, int curve, int group, const void* points_af
     *n_bad = 0;
     *first_bad = n;
     if (!n) return;
-    size_t slice = ctx->points_mul_slice ? ctx->points_mul_slice : pchk::kSliceDefault;
-    slice = (slice + 63) / 64 * 64;
+    size_t slice = slice_lanes(ctx->points_mul_slice);      // points per launch and per temporary device copy
     if (slice > n) slice = n;
     const size_t pb = affine_bytes(curve, group);
     Call k(ctx, 0);

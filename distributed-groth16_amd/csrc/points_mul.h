@@ -34,6 +34,7 @@
 // the oracle and counts the group operations through the Ops parameter.
 #pragma once
 #include "glv_endo.h"
+#include "slices.h"
 #include "types.h"
 
 namespace dg16 {
@@ -241,8 +242,6 @@ DG_HD RrProof<Fq, Fq2> rr_combine(bool ok, const Affine<Fq>& a_inv, const Affine
 namespace dg16 {
 namespace pmul {
 
-constexpr size_t kSliceDefault = (size_t)1 << 16;   // products per launch pair: bounds the table (8 XYZZ per product)
-
 // the table of one lane in the slice's buffer: word-major, lane-minor (see the header comment)
 template <class F>
 struct GlobalTab {
@@ -289,9 +288,8 @@ template <class F, class Fr>
 void points_mul_typed(Call& k, const void* points_dev, const void* scalars_dev, size_t n, unsigned mode, void* out_dev) {
   if (!n) return;
   static_assert(sizeof(Fr) == 32, "scalar size");
-  size_t slice = k.ctx->points_mul_slice ? k.ctx->points_mul_slice : kSliceDefault;
-  slice = (slice + 63) / 64 * 64;
-  const size_t first = n < slice ? (n + 63) / 64 * 64 : slice;      // the stride of every launch of this call
+  const size_t slice = slice_lanes(k.ctx->points_mul_slice);
+  const size_t first = launch_stride(n, slice);      // the stride of every launch of this call
   constexpr size_t W = sizeof(XYZZ<F>) / 4;
   uint32_t* table = (uint32_t*)ws(k.c, 20, (size_t)kTable * W * first * 4);
   XYZZ<F>* acc = (XYZZ<F>*)ws(k.c, 21, first * sizeof(XYZZ<F>));
@@ -310,12 +308,7 @@ void points_mul_typed(Call& k, const void* points_dev, const void* scalars_dev, 
       hipLaunchKernelGGL((points_mul_kernel<F, Fr, false>), grid, block, 0, k.s(), p, s, cnt, (int)(mode & 1u), table,
                          first, acc);
     DG_HIP(hipGetLastError());
-    unsigned per_lane = (unsigned)(cnt >> 13);
-    per_lane = per_lane < 1 ? 1 : per_lane > 32 ? 32 : per_lane;
-    const size_t lanes = (cnt + per_lane - 1) / per_lane;
-    hipLaunchKernelGGL(fb_affine_kernel<F>, dim3((unsigned)((lanes + 63) / 64)), dim3(64), 0, k.s(), acc, pref, cnt,
-                       lanes, per_lane, (Affine<F>*)out_dev + lo);
-    DG_HIP(hipGetLastError());
+    fb_to_affine(k, acc, pref, cnt, (Affine<F>*)out_dev + lo);
   }
   k.end_dominant();
 }

@@ -7,8 +7,8 @@
 //              costs no divergence.
 //   schedule   made on the host once per call (make_schedule): k is split with the group's endomorphism where the rule of
 //              dg16_msm allows it (pmul::may_split: cofactor one, or the caller's in_subgroup), every part is recoded as a
-//              width-w non-adjacent form -- digits odd or zero, |d| < 2^(w-1), two non-zero digits at least w positions
-//              apart -- and the part's sign is folded into its digits.  One 32-bit word per position holds the signed
+//              width-w non-adjacent form (wnaf.h: recode_wnaf) -- digits odd or zero, |d| < 2^(w-1), two non-zero digits
+//              at least w positions apart -- and the part's sign is folded into its digits.  One 32-bit word per position holds the signed
 //              bytes of the (up to four) parts; the rows run from position 0 to the highest position that holds a
 //              non-zero digit of any part.
 //   loop       the kernel reads the row of a position at an address that depends on the position alone: a uniform load,
@@ -16,7 +16,8 @@
 //              non-zero digit, one addition of psi^j(T[|d|]), y negated for d < 0; the endomorphism is applied to the
 //              table entry on the fly (GlvOf<F>::endo_xyzz), as in points_mul.h.  A zero position is a doubling and
 //              nothing else: no dummy addition, no select.  The chain starts at the top row, so no identity is doubled.
-//   table      the odd multiples P, 3P, .. (2^(w-1) - 1) P only: one doubling and 2^(w-2) - 1 additions.
+//   table      the odd multiples P, 3P, .. (2^(w-1) - 1) P only: one doubling and 2^(w-2) - 1 additions (wnaf.h:
+//              build_odd_table).
 //   width      w = 5, by the count (density of a width-w NAF: one non-zero digit in w + 1 positions), table included:
 //                 path      bits x parts   w = 4: additions      w = 5: additions      dg16_points_mul
 //                 plain     255 x 1        3 + 255 / 5 = 54      7 + 255 / 6 = 49.5    67
@@ -26,7 +27,8 @@
 //              table is eight entries, the size and the layout of points_mul.h's (pmul::GlobalTab), and the worst case
 //              (a non-zero digit every w positions) is 7 + ceil(256 / 5) = 59 additions, 7 + 2 * 26 = 59, 7 + 4 * 14 = 63.
 //   budget     doublings: 1 (table) + the top position: at most 256 / 128 / 68.
-//   affine     the accumulators of a slice go through fixed_base_impl.h's batched inversion (fb_affine_kernel).
+//   slices     of slices.h's rule, as dg16_points_mul's.
+//   affine     the accumulators of a slice go through fixed_base_impl.h's batched inversion (fb_to_affine).
 //
 // Exceptional cases of the addition law.  All additions are XYZZ::add, which is complete (identity, equal and opposite
 // operands); nothing is proven away.  They do occur: the accumulator is the identity until the first non-zero digit, an
@@ -37,13 +39,15 @@
 // the oracle and counts the group operations through the Ops parameter.
 #pragma once
 #include "points_mul.h"
+#include "wnaf.h"
 
 namespace dg16 {
 namespace pscale {
 
 constexpr int kWidth = 5;
 constexpr int kTable = 1 << (kWidth - 2);      // entries 1P, 3P, .. 15P
-constexpr int kMaxRows = 260;                  // positions of a scalar below 2^255: at most 256
+using wnaf::kMaxRows;
+using wnaf::row_digit;
 
 // rows[i]: byte j = the signed digit of part j at position i (the part's sign folded in)
 struct Schedule {
@@ -52,70 +56,29 @@ struct Schedule {
   uint32_t rows[kMaxRows];
 };
 
-// the width-w NAF of the 8-word integer m into byte `part` of the rows, negated where neg; returns its length
-inline int recode_wnaf(const uint32_t* m, bool neg, int part, uint32_t* rows) {
-  uint32_t k[9] = {m[0], m[1], m[2], m[3], m[4], m[5], m[6], m[7], 0};
-  int len = 0;
-  for (int pos = 0; pos < kMaxRows; pos++) {
-    uint32_t any = 0;
-    for (int j = 0; j < 9; j++) any |= k[j];
-    if (!any) break;
-    if (k[0] & 1u) {
-      int d = (int)(k[0] & ((1u << kWidth) - 1u));
-      if (d >= (1 << (kWidth - 1))) d -= 1 << kWidth;
-      if (d > 0) {
-        k[0] -= (uint32_t)d;                          // the low w bits are d: no borrow
-      } else {
-        uint64_t c = (uint64_t)(-d);
-        for (int j = 0; j < 9 && c; j++) {
-          c += k[j];
-          k[j] = (uint32_t)c;
-          c >>= 32;
-        }
-      }
-      rows[pos] |= (uint32_t)(uint8_t)(int8_t)(neg ? -d : d) << (8 * part);
-      len = pos + 1;
-    }
-    for (int j = 0; j < 9; j++) k[j] = (k[j] >> 1) | (j + 1 < 9 ? k[j + 1] << 31 : 0u);
-  }
-  return len;
-}
-
 // k: 8 words, below 2^255.  split: use the group's endomorphism (the caller applied pmul::may_split)
 template <class F>
 inline void make_schedule(const uint32_t* k, bool split, Schedule& s) {
-  for (int i = 0; i < kMaxRows; i++) s.rows[i] = 0u;
+  int8_t dig[4][kMaxRows];
+  s.dim = 1;
   s.len = 0;
+  bool done = false;
   if constexpr (GlvOf<F>::enabled) {
     if (split) {
       pmul::SplitScalar<F> parts;
       pmul::split_scalar<F>(k, parts);
       s.dim = GlvOf<F>::DIM;
       for (int j = 0; j < GlvOf<F>::DIM; j++) {
-        const int len = recode_wnaf(parts.mag[j], parts.neg[j], j, s.rows);
+        const int len = wnaf::recode_wnaf<kWidth>(parts.mag[j], parts.neg[j], dig[j]);
         s.len = len > s.len ? len : s.len;
       }
-      return;
+      done = true;
     }
   }
-  s.dim = 1;
-  s.len = recode_wnaf(k, false, 0, s.rows);
-}
-
-DG_HD int row_digit(uint32_t row, int part) { return (int)(int8_t)(row >> (8 * part)); }
-
-// T[j] = (2 j - 1) p, j = 1 .. kTable: one doubling, kTable - 1 additions
-template <class F, class Ops, class Tab>
-DG_HD void build_odd_table(const Affine<F>& p, Ops& ops, Tab& tab) {
-  XYZZ<F> t = XYZZ<F>::from_affine(p);
-  tab.put(1, t);
-  const XYZZ<F> two = ops.dbl(t);
-#if defined(__HIP_DEVICE_COMPILE__)
-#pragma unroll 1
-#endif
-  for (int j = 2; j <= kTable; j++) {
-    t = ops.add(t, two);
-    tab.put(j, t);
+  if (!done) s.len = wnaf::recode_wnaf<kWidth>(k, false, dig[0]);
+  for (int i = 0; i < kMaxRows; i++) {
+    s.rows[i] = 0u;
+    for (int j = 0; j < s.dim; j++) s.rows[i] |= (uint32_t)(uint8_t)dig[j][i] << (8 * j);
   }
 }
 
@@ -135,7 +98,7 @@ DG_HD XYZZ<F> digit_add(const XYZZ<F>& acc, int d, Ops& ops, Tab& tab) {
 // k p under the schedule's rows; DIM = 1 for ANY point of the curve, DIM = 2 / 4 for p in the order-r subgroup
 template <int DIM, class F, class Ops, class Tab>
 DG_HD XYZZ<F> product(const Affine<F>& p, const uint32_t* rows, int len, Ops& ops, Tab& tab) {
-  build_odd_table(p, ops, tab);
+  wnaf::build_odd_table<kTable>(p, ops, tab);
   XYZZ<F> acc = XYZZ<F>::inf();
 #if defined(__HIP_DEVICE_COMPILE__)
 #pragma unroll 1
@@ -194,9 +157,7 @@ void points_scale_typed(Call& k, const void* points_host, const uint32_t* scalar
   if (!n) return;
   Schedule s;
   make_schedule<F>(scalar8, pmul::may_split<F>(in_subgroup), s);
-  size_t slice = k.ctx->points_mul_slice ? k.ctx->points_mul_slice : pmul::kSliceDefault;
-  slice = (slice + 63) / 64 * 64;
-  const size_t stride = n < slice ? (n + 63) / 64 * 64 : slice;
+  const size_t slice = slice_lanes(k.ctx->points_mul_slice), stride = launch_stride(n, slice);
   constexpr size_t W = sizeof(XYZZ<F>) / 4;
   const uint32_t* rows = (const uint32_t*)ws(k.c, 1, sizeof s.rows);
   Affine<F>* p = (Affine<F>*)ws(k.c, 2, stride * sizeof(Affine<F>));
@@ -216,12 +177,7 @@ void points_scale_typed(Call& k, const void* points_host, const uint32_t* scalar
       hipLaunchKernelGGL((points_scale_kernel<F, GlvOf<F>::DIM>), grid, block, 0, k.s(), p, rows, s.len, cnt, table,
                          stride, acc);
     DG_HIP(hipGetLastError());
-    unsigned per_lane = (unsigned)(cnt >> 13);
-    per_lane = per_lane < 1 ? 1 : per_lane > 32 ? 32 : per_lane;
-    const size_t lanes = (cnt + per_lane - 1) / per_lane;
-    hipLaunchKernelGGL(fb_affine_kernel<F>, dim3((unsigned)((lanes + 63) / 64)), dim3(64), 0, k.s(), acc, pref, cnt, lanes,
-                       per_lane, p);
-    DG_HIP(hipGetLastError());
+    fb_to_affine(k, acc, pref, cnt, p);
     DG_HIP(hipMemcpyAsync((Affine<F>*)out_host + lo, p, cnt * sizeof(Affine<F>), hipMemcpyDeviceToHost, k.s()));
   }
   k.end_dominant();

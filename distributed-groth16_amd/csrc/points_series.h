@@ -16,7 +16,7 @@
 //              (SlicePlan) and chunks carry it as uint64_t, and the C entry point refuses a start + n that wraps.
 //   edge cases ratio = 0: pow_u64(0) is one, so the term of exponent 0 is `first` and every other term is 0 (the
 //              identity); first = 0: all identities; ratio = 1: every term is `first`.
-//   slices     of the size dg16_ctx_set_points_mul_slice sets, rounded up to 64 like points_scale.h's: the device copy of
+//   slices     of the size dg16_ctx_set_points_mul_slice sets, by slices.h's rule (slice_lanes): the device copy of
 //              a slice's points (slot 2) and its scalars (slot 1) come from channel 0's workspace; points_mul_run adds
 //              its slots 20 .. 22.
 //
@@ -64,9 +64,9 @@ struct SlicePlan {
   uint64_t exp0;
   size_t chunks;
 };
-DG_HD size_t round_slice(size_t slice) { return (slice + 63) / 64 * 64; }
-DG_HD size_t slice_count(size_t n, size_t slice) { return (n + slice - 1) / slice; }
-// slice: a multiple of 64 (round_slice); start + n does not wrap
+using dg16::round_slice;      // (slices.h's, under the names the plan has been tested by)
+using dg16::slice_count;
+// slice: a multiple of 64 (slices.h: slice_lanes); start + n does not wrap
 DG_HD SlicePlan plan_slice(size_t n, size_t slice, uint64_t start, size_t index) {
   SlicePlan p;
   p.lo = index * slice;
@@ -114,8 +114,7 @@ void points_series_curve(Call& k, int group, const void* points_host, size_t n, 
   memcpy(&first, first8, 32);
   memcpy(&ratio, ratio8, 32);
   const Fr first_m = first.to_mont(), ratio_m = ratio.to_mont();
-  const size_t slice = round_slice(k.ctx->points_mul_slice ? k.ctx->points_mul_slice : pmul::kSliceDefault);
-  const size_t stride = n < slice ? round_slice(n) : slice;
+  const size_t slice = slice_lanes(k.ctx->points_mul_slice), stride = launch_stride(n, slice);
   const size_t pb = affine_bytes(CURVE, group);
   Fr* scal = (Fr*)ws(k.c, 1, stride * sizeof(Fr));
   char* pts = (char*)ws(k.c, 2, stride * pb);

@@ -9,13 +9,14 @@
 //   schedule   made on the host once per (handle, group, split) (make_schedule) and cached in the dg16_pss under its
 //              mutex.  Every M[r][c] is split with the group's endomorphism where the rule of dg16_msm allows it
 //              (pmul::may_split), every part recoded as a width-w non-adjacent form with its sign folded in
-//              (pscale::recode_wnaf's method).  Row r holds, per position, the signed bytes of its l DIM parts -- byte
+//              (wnaf.h: recode_wnaf).  Row r holds, per position, the signed bytes of its l DIM parts -- byte
 //              c * DIM + j is part j of M[r][c], padded to whole 32-bit words -- from position 0 to the highest non-zero
 //              position of any of its parts.
 //   table      kernel 1, one lane per input point of the slice: the odd multiples P, 3P, .. (2^(w-1) - 1) P, one doubling
-//              and 2^(w-2) - 1 additions, written ONCE per point and read by all n rows.  Word t of entry j of point
-//              (e, c) lies at ((c * kTable + j - 1) * W + t) * stride + e: the lanes of a wave of kernel 2 hold
-//              consecutive e and the same c, so they read consecutive words (pmul::GlobalTab with the base moved by c).
+//              and 2^(w-2) - 1 additions (wnaf.h: build_odd_table), written ONCE per point and read by all n rows.  Word
+//              t of entry j of point (e, c) lies at ((c * kTable + j - 1) * W + t) * stride + e: the lanes of a wave of
+//              kernel 2 hold consecutive e and the same c, so they read consecutive words (pmul::GlobalTab with the base
+//              moved by c).
 //   combine    kernel 2, one lane per (e, r), r = blockIdx.y: the digit row is read at an address that depends on r and
 //              the position alone, so every "digit is zero" branch is uniform.  Per position ONE doubling, then one
 //              addition of psi^j(T_c[|d|]) (y negated for d < 0) per non-zero digit; a zero word of the row is skipped
@@ -35,9 +36,10 @@
 //              (l x 4 KB per chunk for BN254 G1, l x 12 KB for a BLS12 G2).  Digits stay signed bytes (|d| <= 63).
 //   budget     doublings per output: 1/4 (table) + the top position of the row: at most 256 / 128 / 68 on the plain /
 //              DIM 2 / DIM 4 paths, whatever l is.  matvec_points_kernel: about 254 l doublings and 127 l additions.
-//   affine     the accumulators of a slice go through fixed_base_impl.h's batched inversion (fb_affine_kernel).
-//   slices     chunks per slice = the context's points_mul_slice / n rounded down to a multiple of 64 (at least 64): the
-//              slice's outputs do not exceed the setting.  Tables, accumulators and staging come from channel 0's workspace.
+//   affine     the accumulators of a slice go through fixed_base_impl.h's batched inversion (fb_to_affine).
+//   slices     chunks per slice = the context's points_mul_slice (slices.h's default) / n rounded down to a multiple of
+//              64 (at least 64): the slice's outputs do not exceed the setting.  Tables, accumulators and staging come
+//              from channel 0's workspace.
 //
 // Exceptional cases of the addition law.  Every addition is XYZZ::add, which is complete.  Inside one chunk they all
 // occur: the accumulator is the identity until the first non-zero digit of a non-identity point, an identity input (the
@@ -56,7 +58,7 @@ namespace ppack {
 
 constexpr int kWidth = 7;
 constexpr int kTable = 1 << (kWidth - 2);      // entries 1P, 3P, .. 63P
-constexpr int kMaxRows = pscale::kMaxRows;     // positions of a part: at most 256
+using wnaf::kMaxRows;                          // positions of a part: at most 256
 constexpr unsigned kMaxL = 8;                  // dg16_pss_create's bound
 
 // The schedule of one (pack matrix, split).  words: 32-bit words per position = ceil(l * dim / 4); row r occupies
@@ -75,37 +77,6 @@ struct Schedule {
     return v;
   }
 };
-
-// the width-w NAF of the 8-word integer m, negated where neg, into digits[0 .. kMaxRows); returns its length
-// (pscale::recode_wnaf's method at this header's width, one signed byte per position)
-inline int recode_wnaf(const uint32_t* m, bool neg, int8_t* digits) {
-  uint32_t k[9] = {m[0], m[1], m[2], m[3], m[4], m[5], m[6], m[7], 0};
-  int len = 0;
-  for (int pos = 0; pos < kMaxRows; pos++) {
-    digits[pos] = 0;
-    uint32_t any = 0;
-    for (int j = 0; j < 9; j++) any |= k[j];
-    if (!any) continue;
-    if (k[0] & 1u) {
-      int d = (int)(k[0] & ((1u << kWidth) - 1u));
-      if (d >= (1 << (kWidth - 1))) d -= 1 << kWidth;
-      if (d > 0) {
-        k[0] -= (uint32_t)d;                          // the low w bits are d: no borrow
-      } else {
-        uint64_t c = (uint64_t)(-d);
-        for (int j = 0; j < 9 && c; j++) {
-          c += k[j];
-          k[j] = (uint32_t)c;
-          c >>= 32;
-        }
-      }
-      digits[pos] = (int8_t)(neg ? -d : d);
-      len = pos + 1;
-    }
-    for (int j = 0; j < 9; j++) k[j] = (k[j] >> 1) | (j + 1 < 9 ? k[j + 1] << 31 : 0u);
-  }
-  return len;
-}
 
 // M: [n][l] canonical scalars of 8 words (below r < 2^255).  split: use the group's endomorphism (the caller applied
 // pmul::may_split)
@@ -133,13 +104,13 @@ inline void make_schedule(const uint32_t* M, unsigned l, bool split, Schedule& s
           pmul::SplitScalar<F> sp;
           pmul::split_scalar<F>(k, sp);
           for (int j = 0; j < GlvOf<F>::DIM; j++) {
-            const int lj = recode_wnaf(sp.mag[j], sp.neg[j], d + (size_t)j * kMaxRows);
+            const int lj = wnaf::recode_wnaf<kWidth>(sp.mag[j], sp.neg[j], d + (size_t)j * kMaxRows);
             len = lj > len ? lj : len;
           }
           done = true;
         }
       }
-      if (!done) len = recode_wnaf(k, false, d);
+      if (!done) len = wnaf::recode_wnaf<kWidth>(k, false, d);
       s.len[r] = len > s.len[r] ? len : s.len[r];
     }
     s.stride = s.len[r] > s.stride ? s.len[r] : s.stride;
@@ -153,19 +124,10 @@ inline void make_schedule(const uint32_t* M, unsigned l, bool split, Schedule& s
       }
 }
 
-// T[j] = (2 j - 1) p, j = 1 .. kTable: one doubling, kTable - 1 additions
+// the table of one input point at this header's width
 template <class F, class Ops, class Tab>
 DG_HD void build_odd_table(const Affine<F>& p, Ops& ops, Tab& tab) {
-  XYZZ<F> t = XYZZ<F>::from_affine(p);
-  tab.put(1, t);
-  const XYZZ<F> two = ops.dbl(t);
-#if defined(__HIP_DEVICE_COMPILE__)
-#pragma unroll 1
-#endif
-  for (int j = 2; j <= kTable; j++) {
-    t = ops.add(t, two);
-    tab.put(j, t);
-  }
+  wnaf::build_odd_table<kTable>(p, ops, tab);
 }
 
 // sum_c M[r][c] P_c under row r's schedule: rows = the row's words, len its positions; tabs.get(c, j) = entry j of the
@@ -188,7 +150,7 @@ DG_HD XYZZ<F> combine(const uint32_t* rows, int len, int words, Ops& ops, const 
 #pragma unroll 1
 #endif
       for (int b = 0; b < 4; b++) {
-        const int d = pscale::row_digit(row, b);
+        const int d = wnaf::row_digit(row, b);
         if (!d) continue;
         const int part = 4 * w + b;
         const int m = d < 0 ? -d : d;
@@ -301,8 +263,8 @@ void pack_points_typed(Call& k, const dg16_pss* pp, int group, const void* point
   const Schedule& s = schedule_of<F>(k, pp, group, pmul::may_split<F>(in_subgroup));
   const std::vector<uint32_t> img = s.image();
   const size_t chunks = chunks_of(n_points, l);
-  const size_t per = slice_chunks(k.ctx->points_mul_slice ? k.ctx->points_mul_slice : pmul::kSliceDefault, n);
-  const size_t stride = chunks < per ? (chunks + 63) / 64 * 64 : per;
+  const size_t per = slice_chunks(k.ctx->points_mul_slice ? k.ctx->points_mul_slice : kSliceDefault, n);
+  const size_t stride = launch_stride(chunks, per);
   constexpr size_t W = sizeof(XYZZ<F>) / 4;
   Affine<F>* p = (Affine<F>*)ws(k.c, 0, stride * l * sizeof(Affine<F>));
   uint32_t* sched = (uint32_t*)ws(k.c, 1, img.size() * 4);
@@ -331,13 +293,7 @@ void pack_points_typed(Call& k, const dg16_pss* pp, int group, const void* point
       hipLaunchKernelGGL((pss_pack_combine_kernel<F, GlvOf<F>::DIM>), grid, block, 0, k.s(), sched, n, s.words, s.stride,
                          cnt, table, stride, acc);
     DG_HIP(hipGetLastError());
-    const size_t outs = cnt * n;
-    unsigned per_lane = (unsigned)(outs >> 13);
-    per_lane = per_lane < 1 ? 1 : per_lane > 32 ? 32 : per_lane;
-    const size_t lanes = (outs + per_lane - 1) / per_lane;
-    hipLaunchKernelGGL(fb_affine_kernel<F>, dim3((unsigned)((lanes + 63) / 64)), block, 0, k.s(), acc, pref, outs, lanes,
-                       per_lane, out);
-    DG_HIP(hipGetLastError());
+    fb_to_affine(k, acc, pref, cnt * n, out);
     // [n][cnt] -> columns lo .. lo + cnt of [n][chunks]
     DG_HIP(hipMemcpy2DAsync((Affine<F>*)shares_host + lo, chunks * sizeof(Affine<F>), out, cnt * sizeof(Affine<F>),
                             cnt * sizeof(Affine<F>), n, hipMemcpyDeviceToHost, k.s()));

@@ -260,13 +260,8 @@ void srs_output(Call& k, const SrsOutput<F>& o, size_t nv, int group, bool in_su
     DevBuf pref(batch * sizeof(F));
     for (size_t lo = 0; lo < nv; lo += kFbBatch) {
       const size_t cnt = nv - lo < kFbBatch ? nv - lo : kFbBatch;
-      unsigned per_lane = (unsigned)(cnt >> 13);
-      per_lane = per_lane < 1 ? 1 : per_lane > 32 ? 32 : per_lane;
-      const size_t lanes = (cnt + per_lane - 1) / per_lane;
-      hipLaunchKernelGGL(fb_affine_kernel<F>, dim3((unsigned)((lanes + 63) / 64)), dim3(64), 0, k.s(),
-                         acc.as<XYZZ<F>>() + lo, pref.as<F>(), cnt, lanes, per_lane, out + lo);
+      fb_to_affine(k, acc.as<XYZZ<F>>() + lo, pref.as<F>(), cnt, out + lo);
     }
-    DG_HIP(hipGetLastError());
     DG_HIP(hipStreamSynchronize(k.s()));
   }
   // ---- MSM wires ------------------------------------------------------------------------------------------------

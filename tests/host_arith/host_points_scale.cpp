@@ -75,6 +75,13 @@ int hs_schedule(int gid, int split, const uint32_t* k, int8_t* digits, int* len)
   BY_GROUP(gid, return schedule<F>(split, k, digits, len));
   return -1;
 }
+// wnaf.h's recoder alone at width w (5 or 7) on the 8-word integer m: digits = kMaxRows signed digits of m, or of -m
+// where neg; returns the length, -1 for another width
+int hs_recode(int w, const uint32_t* m, int neg, int8_t* digits) {
+  if (w == 5) return wnaf::recode_wnaf<5>(m, neg != 0, digits);
+  if (w == 7) return wnaf::recode_wnaf<7>(m, neg != 0, digits);
+  return -1;
+}
 // LAMBDA of the group's split (8 words): k = sum_j part_j LAMBDA^j mod r
 int hs_lambda(int gid, uint32_t* out) {
   BY_GROUP(gid, memcpy(out, GlvOf<F>::C::LAMBDA, 32));
@@ -107,3 +114,32 @@ int hs_invert(int curve, const uint32_t* d, uint32_t* out) {
 }
 
 }  // extern "C"
+
+#if defined(HOST_POINTS_SCALE_MAIN)
+// A stand-alone program for a sanitizer build (tests/test_points_scale_host.py): host_points_scale <file of 8-word
+// integers>.  Per integer one line: the length of the recoder's digits at w = 5, 7 for m and for -m, then, for an integer
+// below 2^255, parts:rows of make_schedule for the six groups on the plain and the split path.
+#include <stdio.h>
+
+int main(int argc, char** argv) {
+  FILE* f = argc == 2 ? fopen(argv[1], "rb") : nullptr;
+  if (!f) {
+    fprintf(stderr, "usage: host_points_scale <file of 8-word integers>\n");
+    return 2;
+  }
+  uint32_t m[8];
+  int8_t digits[4 * pscale::kMaxRows];
+  while (fread(m, 4, 8, f) == 8) {
+    for (int w = 5; w <= 7; w += 2)
+      for (int neg = 0; neg < 2; neg++) printf("%d ", hs_recode(w, m, neg, digits));
+    for (int id = 0; id < 12 && !(m[7] >> 31); id++) {
+      int len = 0;
+      const int dim = hs_schedule(id / 2, id % 2, m, digits, &len);
+      printf("%d:%d ", dim, len);
+    }
+    printf("\n");
+  }
+  fclose(f);
+  return 0;
+}
+#endif

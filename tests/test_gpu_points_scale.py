@@ -4,6 +4,7 @@ of products per group go against the oracle (`corc.point_mul`) as well.  The sca
 (tests/points_scale_cases.py)."""
 
 import ctypes
+import random
 import time
 
 import numpy as np
@@ -12,6 +13,7 @@ import pytest
 import points_mul_cases as PM
 import points_scale_cases as PS
 from oracle import corc
+from oracle.pyref.curves import CURVES
 from oracle.pyref.fields import FR
 from gpu_util import ctx
 from test_gpu_points_mul import _neg
@@ -97,6 +99,32 @@ def test_partial_waves_and_slices(curve, group, in_subgroup):
     finally:
         c.set_points_mul_slice(0)
     assert np.array_equal(got, replicated(curve, group, pts, r - 1, in_subgroup))
+
+
+@pytest.mark.parametrize("curve,group,n", [("bn254", 1, 16383), ("bn254", 1, 16384), ("bn254", 1, 16385),
+                                           ("bn254", 1, 32769), ("bls12_381", 2, 16385)])
+def test_affine_tail_with_several_points_per_lane(curve, group, n):
+    """The batched inversion behind every product call (fb_to_affine) gives lane t the points t, t + lanes, ..: one per
+    lane up to n = 16383, two from 16384 on (8192 lanes, even; at 16385 the last of 8193 lanes has no second point),
+    four at 32769 (8193 lanes, ragged).  Default slice, so one launch.  Input i G from dg16_fixed_base_mul with identities
+    at 0, n - 1 and on either side of `lanes`; 5 P and then 5^-1 (5 P) must give the input back byte for byte, and eight
+    seeded products equal the oracle's."""
+    r = FR[curve].p
+    per_lane = min(max(n >> 13, 1), 32)
+    lanes = -(-n // per_lane)
+    assert (per_lane, lanes) == {16383: (1, 16383), 16384: (2, 8192), 16385: (2, 8193), 32769: (4, 8193)}[n]
+    c = ctx()
+    pts = c.fixed_base_mul(curve, group, corc.ints_to_arr(list(range(n)), 4))
+    holes = sorted({0, n - 1, lanes - 1, min(lanes, n - 1)})
+    pts[holes] = 0
+    out = c.points_scale(curve, group, pts, 5, in_subgroup=True)
+    back = c.points_scale(curve, group, out, pow(5, r - 2, r), in_subgroup=True)
+    assert np.array_equal(back, pts)
+    assert np.flatnonzero(~out.any(axis=1)).tolist() == holes
+    cv = CURVES[curve, "g%d" % group]
+    for i in random.Random(n).sample(range(n), 8):
+        exp = np.zeros_like(out[i]) if i in holes else PM.pack_point(curve, group, cv.mul(cv.gen, 5 * i))
+        assert np.array_equal(out[i], exp), i
 
 
 @pytest.mark.parametrize("curve,group", [("bn254", 1), ("bls12_381", 2), ("bls12_377", 1)])

@@ -4,6 +4,7 @@ operations are counted by the shim's Ops and held against dg16_points_mul's rows
 
 import ctypes
 import os
+import random
 import subprocess
 
 import numpy as np
@@ -26,14 +27,15 @@ PATHS = [(c, g, s) for c, g in PM.GROUPS for s in (0, 1)]
 
 @pytest.fixture(scope="module")
 def hs():
-    hdrs = [os.path.join(CSRC, f) for f in ("points_scale.h", "points_mul.h", "glv_endo.h", "glv.h", "fp.h", "fp2.h",
-                                            "ec.h", "types.h", "consts_gen.h")]
+    hdrs = [os.path.join(CSRC, f) for f in ("points_scale.h", "wnaf.h", "points_mul.h", "slices.h", "glv_endo.h", "glv.h",
+                                            "fp.h", "fp2.h", "ec.h", "types.h", "consts_gen.h")]
     if not os.path.exists(SO) or any(os.path.getmtime(SO) < os.path.getmtime(p) for p in [SRC] + hdrs):
         subprocess.check_call(["g++", "-O2", "-std=c++17", "-Wno-unknown-pragmas", "-shared", "-fPIC", "-o", SO, SRC])
     L = ctypes.CDLL(SO)
     vp, sz, i = ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int
     L.hs_params.argtypes = [vp]
     L.hs_schedule.argtypes = [i, i, vp, vp, vp]
+    L.hs_recode.argtypes = [i, vp, i, vp]
     L.hs_lambda.argtypes = [i, vp]
     L.hs_scale.argtypes = [i, i, vp, vp, sz, vp, vp]
     L.hs_invert.argtypes = [i, vp, vp]
@@ -94,6 +96,61 @@ def test_schedule_is_a_width_w_naf_of_the_scalar(hs, curve, group, split):
             assert total == k, hex(k)
         else:
             assert (total - k) % r == 0, hex(k)
+
+
+def _recoder_integers(w):
+    """0, 1, 2^w - 1, 2^(w-1) (and the odd value next to it, the first whose digit is negative), 2^255 - 1, r - 1 of each
+    curve and 64 seeded random values below 2^256"""
+    rng = random.Random(77)
+    return ([0, 1, (1 << w) - 1, 1 << (w - 1), (1 << (w - 1)) + 1, (1 << 255) - 1]
+            + [FR[c].p - 1 for c in ("bn254", "bls12_381", "bls12_377")] + [rng.randrange(1 << 256) for _ in range(64)])
+
+
+def _recode(hs, w, m, neg):
+    max_rows = _params(hs)[2]
+    digits = np.full(max_rows, 99, dtype=np.int8)
+    n = hs.hs_recode(w, _p(_words(m)), neg, _p(digits))
+    assert 0 <= n <= max_rows and not digits[n:].any()     # every position is written; none past the length is set
+    return [int(v) for v in digits[:n]]
+
+
+@pytest.mark.parametrize("w", [5, 7])
+def test_the_shared_recoder_is_the_textbook_width_w_naf(hs, w):
+    """wnaf.h's recode_wnaf at the widths of points_scale.h and pss_pack.h, on the same integers, against the definition:
+    digits odd or zero, |d| < 2^(w-1), non-zero digits at least w apart, sum d_i 2^i = m, or -m with the sign folded in;
+    the length ends at a non-zero digit."""
+    for m in _recoder_integers(w):
+        for neg in (0, 1):
+            d = _recode(hs, w, m, neg)
+            nz = [i for i, v in enumerate(d) if v]
+            assert all(d[i] % 2 == 1 and abs(d[i]) < 1 << (w - 1) for i in nz), (hex(m), neg)
+            assert all(b - a >= w for a, b in zip(nz, nz[1:])), (hex(m), neg)
+            assert sum(v << i for i, v in enumerate(d)) == (-m if neg else m), (hex(m), neg)
+            assert len(d) == (nz[-1] + 1 if nz else 0), (hex(m), neg)
+    assert hs.hs_recode(6, _p(_words(1)), 0, _p(np.zeros(_params(hs)[2], dtype=np.int8))) == -1
+
+
+def test_recoder_and_schedule_under_the_sanitizers(hs, tmp_path):
+    """The same text as a stand-alone program under the address and undefined-behaviour sanitizers, on the integers of
+    both widths: a clean run, and the lengths it prints are those of the library above."""
+    exe = str(tmp_path / "host_points_scale")
+    subprocess.check_call(["g++", "-O1", "-g", "-std=c++17", "-Wno-unknown-pragmas", "-fsanitize=address,undefined",
+                           "-fno-sanitize-recover=undefined", "-DHOST_POINTS_SCALE_MAIN", "-o", exe, SRC])
+    ms = _recoder_integers(5) + _recoder_integers(7)
+    fin = tmp_path / "integers.bin"
+    fin.write_bytes(b"".join(m.to_bytes(32, "little") for m in ms))
+    res = subprocess.run([exe, str(fin)], capture_output=True, text=True, timeout=600)
+    assert res.returncode == 0 and not res.stderr, res.stderr[-2000:]
+    lines = res.stdout.splitlines()
+    assert len(lines) == len(ms)
+    for m, line in zip(ms, lines):
+        want = [str(len(_recode(hs, w, m, neg))) for w in (5, 7) for neg in (0, 1)]
+        if m < 1 << 255:
+            for g in range(6):
+                for split in (0, 1):
+                    dim, _, rows = _schedule(hs, g, split, m)
+                    want.append("%d:%d" % (dim, rows))
+        assert line.split() == want, hex(m)
 
 
 def _subgroup_points(curve, group):
