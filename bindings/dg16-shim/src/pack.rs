@@ -91,3 +91,106 @@ pub fn scalars_as_bytes_mut<F: PrimeField>(s: &mut [F]) -> &mut [u8] {
     assert_eq!(core::mem::size_of::<F>(), 32);
     unsafe { core::slice::from_raw_parts_mut(s.as_mut_ptr().cast::<u8>(), s.len() * 32) }
 }
+
+// ---- packing scalars into party shares (`dg16_fr_expand`, `dg16_pss_pack_scalars`, `dg16_request_pack`) ---------------
+
+/// How a vector is cut into the l-tuples that are packed (`DG16_PACK_CHUNKS` / `DG16_PACK_DFFT`).
+#[derive(Clone, Copy, Debug, PartialEq, Eq)]
+pub enum PackLayout {
+    /// consecutive l-chunks, the last one zero-padded (`pack_from_witness`, groth16/examples/sha256.rs:97-121)
+    Chunks = 0,
+    /// bit-reversed, then `(x[e], x[e + m/l], ..)` (`QAP::pss`, groth16/src/qap.rs:151-165)
+    Dfft = 1,
+}
+
+/// Elements `first .. first + n` of stream `stream` of a 32-byte seed, made on the device (`dg16_fr_expand`).
+pub fn fr_expand<F: crate::Dg16Scalar>(seed: &[u8; 32], stream: u64, first: u64, n: usize) -> Result<Vec<F>, crate::Dg16Error> {
+    let mut out = vec![F::zero(); n];
+    crate::check(unsafe {
+        crate::sys::dg16_fr_expand(crate::CTX.0, F::CURVE, seed.as_ptr().cast(), stream, first, n, 1,
+                                   scalars_as_bytes_mut(&mut out).as_mut_ptr().cast())
+    })?;
+    Ok(out)
+}
+
+/// `pack_from_public` (blinds = None) or `pack_from_public_rand` with the caller's randomness
+/// (secret-sharing/src/pss.rs:72-92) over a whole vector for ALL parties: element i of the result is party i's share
+/// vector.  `blinds`: `chunks * l` elements, slot k of chunk e at `e * l + k`.
+#[cfg(feature = "mpc")]
+pub fn pack_scalars<F: PrimeField>(values: &[F], layout: PackLayout, blinds: Option<&[F]>, pp: &crate::net::Pss,
+                                   n_parties: usize) -> Result<Vec<Vec<F>>, crate::Dg16Error> {
+    use crate::sys;
+    if values.is_empty() {
+        return Ok(vec![Vec::new(); n_parties]);
+    }
+    let chunks = unsafe { sys::dg16_pss_scalar_chunks(pp.0, layout as i32, values.len()) };
+    // n = 4 l parties: a blind vector holds chunks * l elements
+    if blinds.map_or(false, |b| b.len() * 4 != chunks * n_parties) {
+        return Err(crate::Dg16Error::LengthMismatch(blinds.map_or(0, |b| b.len())));
+    }
+    let mut flat = vec![F::zero(); n_parties * chunks];
+    crate::check(unsafe {
+        sys::dg16_pss_pack_scalars(crate::CTX.0, pp.0, layout as i32, scalars_as_bytes(values).as_ptr().cast(), values.len(),
+                                   blinds.map_or(core::ptr::null(), |b| scalars_as_bytes(b).as_ptr().cast()),
+                                   scalars_as_bytes_mut(&mut flat).as_mut_ptr().cast())
+    })?;
+    Ok(flat.chunks(chunks.max(1)).take(n_parties).map(|c| c.to_vec()).collect())
+}
+
+/// One party's part of a packed proof request: the `PackedQAPShare` vectors and the two witness share vectors.
+#[cfg(feature = "mpc")]
+pub struct RequestShare<F> {
+    pub a: Vec<F>,
+    pub b: Vec<F>,
+    pub c: Vec<F>,
+    pub a_share: Vec<F>,
+    pub ax_share: Vec<F>,
+}
+
+/// `QAP::pss` (qap.rs:143-187) and the two `pack_from_witness` (sha256.rs:97-121) of a proof request for ALL parties in
+/// one `dg16_request_pack`.  `seed`: 32 uniform bytes of the caller's randomness, used for this request only; every
+/// chunk is then packed as by `pack_from_public_rand` with blinds expanded from the seed on the device.  None packs
+/// plainly.
+#[cfg(feature = "mpc")]
+pub fn pack_request<F: PrimeField>(a: &[F], b: &[F], c: &[F], full_assignment: &[F], num_inputs: usize,
+                                   seed: Option<&[u8; 32]>, pp: &crate::net::Pss, n_parties: usize)
+    -> Result<Vec<RequestShare<F>>, crate::Dg16Error> {
+    use crate::sys;
+    let (m, l) = (a.len(), n_parties / 4);      // n = 4 l (pss.rs:36)
+    if b.len() != m || c.len() != m {
+        return Err(crate::Dg16Error::LengthMismatch(m.min(b.len()).min(c.len())));
+    }
+    if m == 0 || !m.is_power_of_two() || full_assignment.is_empty() || l == 0 {
+        return Err(crate::Dg16Error::Status(sys::DG16_ERR_BAD_ARG, "a, b, c: a power of two; a non-empty assignment".into()));
+    }
+    let num_vars = full_assignment.len();
+    let (cq, ca, cx) = (m / l, (num_vars - 1 + l - 1) / l, (num_vars.saturating_sub(num_inputs) + l - 1) / l);
+    let mut bufs = [vec![F::zero(); n_parties * cq], vec![F::zero(); n_parties * cq], vec![F::zero(); n_parties * cq],
+                    vec![F::zero(); n_parties * ca], vec![F::zero(); n_parties * cx]];
+    let out = {
+        let [oa, ob, oc, os, ox] = &mut bufs;
+        sys::Dg16RequestShares {
+            a: scalars_as_bytes_mut(oa).as_mut_ptr().cast(),
+            b: scalars_as_bytes_mut(ob).as_mut_ptr().cast(),
+            c: scalars_as_bytes_mut(oc).as_mut_ptr().cast(),
+            a_share: scalars_as_bytes_mut(os).as_mut_ptr().cast(),
+            ax_share: scalars_as_bytes_mut(ox).as_mut_ptr().cast(),
+        }
+    };
+    crate::check(unsafe {
+        sys::dg16_request_pack(crate::CTX.0, pp.0, m.trailing_zeros(), scalars_as_bytes(a).as_ptr().cast(),
+                               scalars_as_bytes(b).as_ptr().cast(), scalars_as_bytes(c).as_ptr().cast(),
+                               scalars_as_bytes(full_assignment).as_ptr().cast(), num_vars, num_inputs,
+                               seed.map_or(core::ptr::null(), |s| s.as_ptr().cast()), 1, &out)
+    })?;
+    let row = |v: &Vec<F>, per: usize, i: usize| v[i * per..(i + 1) * per].to_vec();
+    Ok((0..n_parties)
+        .map(|i| RequestShare {
+            a: row(&bufs[0], cq, i),
+            b: row(&bufs[1], cq, i),
+            c: row(&bufs[2], cq, i),
+            a_share: row(&bufs[3], ca, i),
+            ax_share: row(&bufs[4], cx, i),
+        })
+        .collect())
+}

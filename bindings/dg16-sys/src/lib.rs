@@ -191,6 +191,18 @@ pub struct Dg16PkShares {
     pub w: *mut c_void,
     pub h: *mut c_void,
 }
+/// `dg16_request_shares`: the five outputs of `dg16_request_pack`, each party-major `[n][chunks]` field elements
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct Dg16RequestShares {
+    pub a: *mut c_void,
+    pub b: *mut c_void,
+    pub c: *mut c_void,
+    pub a_share: *mut c_void,
+    pub ax_share: *mut c_void,
+}
+pub const DG16_PACK_CHUNKS: c_int = 0;
+pub const DG16_PACK_DFFT: c_int = 1;
 /// `dg16_phase2_report`: what `dg16_groth16_verify_contribution` found (failed = 0: accepted; the DG16_P2_* bits below)
 #[repr(C)]
 #[derive(Clone, Copy, Debug, Default, PartialEq, Eq)]
@@ -440,6 +452,17 @@ extern "C" {
     pub fn dg16_pk_pack(ctx: *mut Dg16Ctx, pp: *const Dg16Pss, num_vars: usize, num_inputs: usize, domain_size: usize,
                         a_query: *const c_void, b_g1_query: *const c_void, b_g2_query: *const c_void,
                         h_query: *const c_void, l_query: *const c_void, out: *const Dg16PkShares, in_subgroup: c_int) -> c_int;
+    // a 32-byte seed stretched into field elements on the device; pack_from_public / pack_from_public_rand over a scalar
+    // vector for ALL parties (layout: DG16_PACK_*; blinds may be null), and a whole proof request (seed32 may be null);
+    // host pointers, synchronous, channel 0; without blinds byte-equal to dg16_pss_apply(which = 0), party-major
+    pub fn dg16_fr_expand(ctx: *mut Dg16Ctx, curve: c_int, seed32: *const c_void, stream: u64, first: u64, n: usize,
+                          mont: c_int, out: *mut c_void) -> c_int;
+    pub fn dg16_pss_scalar_chunks(pp: *const Dg16Pss, layout: c_int, n_values: usize) -> usize;
+    pub fn dg16_pss_pack_scalars(ctx: *mut Dg16Ctx, pp: *const Dg16Pss, layout: c_int, values: *const c_void,
+                                 n_values: usize, blinds: *const c_void, shares: *mut c_void) -> c_int;
+    pub fn dg16_request_pack(ctx: *mut Dg16Ctx, pp: *const Dg16Pss, log_m: c_uint, a: *const c_void, b: *const c_void,
+                             c: *const c_void, full_assignment: *const c_void, num_vars: usize, num_inputs: usize,
+                             seed32: *const c_void, mont: c_int, out: *const Dg16RequestShares) -> c_int;
     // file formats, proof codec, verifier (host code of the library)
     pub fn dg16_io_error() -> *const c_char;
     pub fn dg16_r1cs_parse(data: *const c_void, bytes: usize, out: *mut *mut Dg16R1cs) -> c_int;

@@ -5,6 +5,7 @@
 #include <thread>
 
 #include "dist_impl.h"
+#include "pss_scalars.h"
 
 using namespace dg16;
 
@@ -286,8 +287,10 @@ const TwiddleSet& Dist<Fr>::twiddles(Call& k, int curve, unsigned log_n, int inv
 template <class Fr>
 static void pss_build(dg16_pss* pp) {
   const unsigned n = pp->n, l = pp->l;
-  DG_HIP(hipMalloc(&pp->mats, (6 * n * l + n) * sizeof(Fr)));
+  DG_HIP(hipMalloc(&pp->mats, (6 * n * l + n + n * l) * sizeof(Fr)));
   hipLaunchKernelGGL(pss_setup_kernel<Fr>, dim3(1), dim3(256), 0, 0, l, (Fr*)pp->mats);
+  // the blind columns of pack_from_public_rand, appended: no existing block moves (pss_scalars.h)
+  hipLaunchKernelGGL(pscal::pss_blind_cols_kernel<Fr>, dim3(1), dim3(256), 0, 0, l, (Fr*)pp->mats + 6 * n * l + n);
   DG_HIP(hipGetLastError());
   DG_HIP(hipDeviceSynchronize());
 }

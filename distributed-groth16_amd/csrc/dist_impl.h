@@ -21,6 +21,7 @@ struct dg16_pss {
   int curve;
   unsigned l, t, n;
   void* mats;   // device: pack [n][l] | unpack [l][n] | unpack2 [l][n] | (canonical copies of the three) | v2sum [n] canonical
+                // | blind [n][l]: columns l .. 2 l of the pack matrix, Montgomery form (pss_scalars.h)
   // dg16_pss_pack_points (pss_pack.h): the host schedule of the pack matrix per [group - 1][split], made on first use
   // under sched_mu (parties are host threads) and kept for the handle's life
   mutable std::mutex sched_mu;

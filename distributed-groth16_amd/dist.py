@@ -81,6 +81,37 @@ class PackedSharingParams:
                                                       1 if in_subgroup else 0))
         return out
 
+    def scalar_chunks(self, layout, n_values):
+        return int(self.ctx.L.dg16_pss_scalar_chunks(self.h, int(layout), int(n_values)))
+
+    def pack_scalars(self, values, layout, blinds=None):
+        """`dg16_pss_pack_scalars`: the shares of ALL parties of a scalar vector, party-major: [n][chunks][4].  layout:
+        PACK_CHUNKS (l-chunks, the last one zero-padded: pack_from_witness) or PACK_DFFT (a power of two of at least l
+        values, bit-reversed and read at stride m / l: QAP::pss).  blinds: None (pack_from_public) or [chunks][l]
+        field elements in the form of `values`, the caller's randomness for the upper l slots of the secret domain
+        (pack_from_public_rand, pss.rs:72-82).  Host arrays; synchronous."""
+        vals = np.ascontiguousarray(values, dtype=np.uint64).reshape(-1, 4)
+        nv = vals.shape[0]
+        chunks = self.scalar_chunks(layout, nv)
+        out = np.zeros((self.n, chunks, 4), dtype=np.uint64)
+        if blinds is not None:
+            blinds = np.ascontiguousarray(blinds, dtype=np.uint64)
+            if blinds.size != chunks * self.l * 4:
+                raise ValueError("blinds must hold chunks * l field elements")
+        self.ctx._chk(self.ctx.L.dg16_pss_pack_scalars(self.ctx.h, self.h, int(layout), _ptr(vals) if nv else None, nv,
+                                                       _ptr(blinds) if blinds is not None and blinds.size else None,
+                                                       _ptr(out) if out.size else None))
+        return out
+
+    def pack_from_public_rand(self, secrets, blinds):   # [count][l], [count][l] -> [count][n]
+        """pack_from_public_rand (pss.rs:72-82) with the caller's randomness in place of the reference's test_rng."""
+        secrets = np.ascontiguousarray(secrets, dtype=np.uint64).reshape(-1, self.l, 4)
+        shares = self.pack_scalars(secrets, PACK_CHUNKS, np.ascontiguousarray(blinds, dtype=np.uint64))
+        return np.ascontiguousarray(shares.transpose(1, 0, 2))
+
+
+PACK_CHUNKS, PACK_DFFT = 0, 1      # DG16_PACK_CHUNKS, DG16_PACK_DFFT
+
 
 class LocalTestNet:
     """n parties in one process; party(i) is the handle the i-th caller passes to the d_* functions."""

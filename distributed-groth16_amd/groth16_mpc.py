@@ -5,6 +5,8 @@ from the dist-primitives mirror (dist.py).  Names follow the reference:
     pack_from_arkworks_proving_key     PackedProvingKeyShare::...             groth16/src/proving_key.rs:35-110
     pack_proving_key                   the same through dg16_pk_pack (one call, all parties)
     pack_from_witness                  examples/sha256.rs:97-121
+    pack_request                       qap_pss and the two pack_from_witness through dg16_request_pack (one call, all
+                                       parties, optionally blinded: pack_from_public_rand, pss.rs:72-82)
     A / B / C .compute                 groth16/src/prove.rs:21-136
     party_prove                        `dsha256`                              groth16/examples/sha256.rs:26-95
 
@@ -16,7 +18,7 @@ import ctypes
 import numpy as np
 
 from . import dist as D
-from .lib import FQ_LIMBS64, PkShares, _ptr
+from .lib import FQ_LIMBS64, PkShares, RequestShares, _ptr, _seed32
 
 
 def _bitrev_perm(n):
@@ -48,6 +50,33 @@ def pack_from_witness(pp, assignment):
         a = np.concatenate([a, np.zeros((pad, 4), dtype=np.uint64)])
     packed = pp.pack_from_public(a.reshape(-1, pp.l, 4))
     return [np.ascontiguousarray(packed[:, i]) for i in range(pp.n)]
+
+
+def pack_request(pp, a, b, c, assignment, num_inputs, seed=None, mont=True):
+    """What a client sends for one proof through ONE `dg16_request_pack`: per party (qap_share, a_share, ax_share), with
+    qap_share = the tuple qap_pss returns and a_share / ax_share = pack_from_witness of assignment[1:] /
+    assignment[num_inputs:] -- byte for byte without a seed.  seed: 32 bytes of the CALLER's randomness; every chunk is
+    then packed with blinds (pack_from_public_rand, pss.rs:72-82) expanded from the seed on the device, so that fewer
+    than t + 1 = l servers learn nothing of the witness.  mont: the form a, b, c and the assignment are in."""
+    ctx = pp.ctx
+    v = [np.ascontiguousarray(x, dtype=np.uint64).reshape(-1, 4) for x in (a, b, c)]
+    w = np.ascontiguousarray(assignment, dtype=np.uint64).reshape(-1, 4)
+    m, num_vars = v[0].shape[0], w.shape[0]
+    if m == 0 or m & (m - 1) or any(x.shape[0] != m for x in v):
+        raise ValueError("a, b, c must have the same power-of-two length")
+    log_m = m.bit_length() - 1
+    out = {"a": np.zeros((pp.n, m // pp.l, 4), dtype=np.uint64),
+           "b": np.zeros((pp.n, m // pp.l, 4), dtype=np.uint64),
+           "c": np.zeros((pp.n, m // pp.l, 4), dtype=np.uint64),
+           "a_share": np.zeros((pp.n, -(-max(num_vars - 1, 0) // pp.l), 4), dtype=np.uint64),
+           "ax_share": np.zeros((pp.n, -(-max(num_vars - int(num_inputs), 0) // pp.l), 4), dtype=np.uint64)}
+    ptr = lambda x: _ptr(x).value if x.size else None          # noqa: E731
+    shares = RequestShares(**{k: ptr(x) for k, x in out.items()})
+    seed = None if seed is None else _seed32(seed)
+    ctx._chk(ctx.L.dg16_request_pack(ctx.h, pp.h, log_m, ptr(v[0]), ptr(v[1]), ptr(v[2]), ptr(w), num_vars,
+                                     int(num_inputs), _ptr(seed), 1 if mont else 0, ctypes.byref(shares)))
+    return [(tuple(np.ascontiguousarray(out[k][i]) for k in ("a", "b", "c")), np.ascontiguousarray(out["a_share"][i]),
+             np.ascontiguousarray(out["ax_share"][i])) for i in range(pp.n)]
 
 
 def _packexp_chunks(pp, group, pts):

@@ -79,6 +79,10 @@ class PkShares(ctypes.Structure):         # dg16_pk_shares
     _fields_ = [(n, ctypes.c_void_p) for n in ("s", "u", "v", "w", "h")]
 
 
+class RequestShares(ctypes.Structure):    # dg16_request_shares
+    _fields_ = [(n, ctypes.c_void_p) for n in ("a", "b", "c", "a_share", "ax_share")]
+
+
 class Phase2ReportC(ctypes.Structure):    # dg16_phase2_report
     _fields_ = [("failed", ctypes.c_uint32), ("bad_array", ctypes.c_uint32), ("bad_index", ctypes.c_uint64),
                 ("n_bad_points", ctypes.c_uint64)]
@@ -312,6 +316,11 @@ def load():
     L.dg16_pss_pack_chunks.argtypes = [vp, sz]
     L.dg16_pss_pack_chunks.restype = sz
     L.dg16_pk_pack.argtypes = [vp, vp, sz, sz, sz, vp, vp, vp, vp, vp, ctypes.POINTER(PkShares), i]
+    L.dg16_fr_expand.argtypes = [vp, i, vp, ctypes.c_uint64, ctypes.c_uint64, sz, i, vp]
+    L.dg16_pss_scalar_chunks.argtypes = [vp, i, sz]
+    L.dg16_pss_scalar_chunks.restype = sz
+    L.dg16_pss_pack_scalars.argtypes = [vp, vp, i, vp, sz, vp, vp]
+    L.dg16_request_pack.argtypes = [vp, vp, u, vp, vp, vp, vp, sz, sz, vp, i, ctypes.POINTER(RequestShares)]
     _lib = L
     return L
 
@@ -340,7 +349,8 @@ EXPORTED = ["dg16_ctx_create", "dg16_ctx_destroy", "dg16_last_error", "dg16_set_
             "dg16_groth16_setup_srs", "dg16_setup_srs_limits", "dg16_group_ntt", "dg16_srs_prepare",
             "dg16_points_check", "dg16_srs_verify", "dg16_points_scale", "dg16_groth16_contribute",
             "dg16_groth16_verify_contribution", "dg16_pss_pack_points", "dg16_pss_pack_chunks", "dg16_pk_pack",
-            "dg16_points_mul_series", "dg16_srs_contribute", "dg16_srs_verify_contribution"]
+            "dg16_points_mul_series", "dg16_srs_contribute", "dg16_srs_verify_contribution",
+            "dg16_fr_expand", "dg16_pss_scalar_chunks", "dg16_pss_pack_scalars", "dg16_request_pack"]
 
 
 def _ptr(x):
@@ -363,6 +373,14 @@ def _scalar32(x):
     if not 0 <= x < 1 << 256:
         raise ValueError("a scalar is 32 bytes")
     return np.frombuffer(x.to_bytes(32, "little"), dtype=np.uint64).copy()
+
+
+def _seed32(seed):
+    """32 bytes (bytes-like or a uint8 array) as a uint8 [32] array."""
+    seed = np.frombuffer(bytes(seed), dtype=np.uint8).copy()
+    if seed.size != 32:
+        raise ValueError("a seed is 32 bytes")
+    return seed
 
 
 class ResidentBases:
@@ -836,6 +854,19 @@ class Context:
         n = points.shape[0]
         self._chk(self.L.dg16_points_mul_series(self.h, CURVES[curve], group, _ptr(points) if n else None, n, _ptr(f),
                                                 _ptr(q), start, _ptr(out) if n else None, int(bool(in_subgroup))))
+        return out
+
+    def fr_expand(self, curve, seed, stream, first, n, mont=False):
+        """Elements first .. first + n of stream `stream` of a 32-byte seed (`dg16_fr_expand`), made on the device:
+        int_le(SHA-256(msg(0)) || SHA-256(msg(1))) mod r with msg(j) = "dg16fe" || seed || le64(stream) || le64(index)
+        || byte(j).  uint64 [n][4], Montgomery form if mont, else canonical.  Synchronous."""
+        seed = _seed32(seed)
+        stream, first, n = int(stream), int(first), int(n)
+        if not (0 <= stream < 1 << 64 and 0 <= first < 1 << 64):
+            raise ValueError("stream and first are 64-bit unsigned integers")
+        out = np.zeros((n, 4), dtype=np.uint64)
+        self._chk(self.L.dg16_fr_expand(self.h, CURVES[curve], _ptr(seed), stream, first, n, int(bool(mont)),
+                                        _ptr(out) if n else None))
         return out
 
     @staticmethod

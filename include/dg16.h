@@ -670,6 +670,63 @@ int dg16_pk_pack(dg16_ctx *ctx, const dg16_pss *pp, size_t num_vars, size_t num_
                  const void *a_query, const void *b_g1_query, const void *b_g2_query, const void *h_query,
                  const void *l_query, const dg16_pk_shares *out, int in_subgroup);
 
+/* Element first + i of stream `stream` of a 32-byte seed, i < n: the caller's randomness stretched on the device, so that
+ * only the seed crosses the bus.  With msg(j) = "dg16fe" || seed32[32] || le64(stream) || le64(first + i) || byte(j) (55
+ * bytes: one SHA-256 compression each), the element is int_le(SHA-256(msg(0)) || SHA-256(msg(1))) mod r: a 512-bit
+ * integer reduced, so the bias is below 2^-250.  out: n x 32 bytes, Montgomery form if mont != 0, else canonical.
+ * Streams are independent; a (seed, stream, index) is one element whatever first and n a call uses.
+ * seed32 and out are HOST pointers.  Synchronous: the call runs on channel 0 and out is complete on return.  n = 0 is
+ * DG16_OK and writes nothing.  A NULL seed, a NULL out with n > 0, n >= 2^30 or first + n above 2^64 - 1:
+ * DG16_ERR_BAD_ARG, and nothing is written; an unknown curve is DG16_ERR_BAD_CURVE. */
+int dg16_fr_expand(dg16_ctx *ctx, int curve, const void *seed32, uint64_t stream, uint64_t first, size_t n, int mont,
+                   void *out);
+
+/* Packed shares of a scalar vector, all parties at once, plain (pack_from_public, secret-sharing/src/pss.rs:86-92) or
+ * hiding (pack_from_public_rand, pss.rs:72-82, tested at :209-240).  shares: party-major, [pp->n][chunks] field elements,
+ * chunks = dg16_pss_scalar_chunks(pp, layout, n_values).
+ * layout: DG16_PACK_CHUNKS -- chunk e holds values[e l .. e l + l), the last one padded with zeros (pack_from_witness,
+ * groth16/examples/sha256.rs:97-121), chunks = ceil(n_values / l).  DG16_PACK_DFFT -- n_values = m, a power of two with
+ * m >= l; chunk e holds (x[e], x[e + m / l], ..) with x the bit-reversed vector (QAP::pss, groth16/src/qap.rs:151-165),
+ * chunks = m / l.
+ * blinds: NULL, or [chunks][l] field elements in the form of `values` (the map is linear, so Montgomery in gives
+ * Montgomery out and canonical canonical).  Slot k of chunk e goes to position l + k of the secret domain, whose upper
+ * l = t + 1 positions pack_from_public leaves at zero.  With blinds drawn uniformly by the caller any t parties' shares
+ * are independent of the values; dg16_pss_apply(which = 1) and the protocols built on it drop the blind slots.
+ * THE CONTRACT: with blinds == NULL the result equals dg16_pss_apply(which = 0) on the same chunks, transposed to
+ * party-major, BYTE FOR BYTE.
+ * values, blinds and shares are HOST pointers.  Synchronous: the call runs on channel 0, is ordered behind the work
+ * enqueued on channel 0's stream, and the shares are complete on return.  A large input runs in slices of chunks whose
+ * shares do not exceed what dg16_ctx_set_points_mul_slice sets, rounded down to a multiple of 64 chunks and never below
+ * 64 chunks (a setting under 64 n is therefore exceeded: a slice is 64 chunks = 64 n shares).  Where the context sets
+ * nothing the default here is 2^21 share elements (64 MB), not the 2^16 of the point calls that share the setting: a
+ * share is 32 bytes and has no table.  The slices come from channel 0's workspace, a DG16_PACK_DFFT input is resident in full for the call, and DG16_ERR_OOM leaves the
+ * context usable.
+ * n_values = 0 is DG16_OK and writes nothing.  A NULL values or shares with n_values > 0, another layout, an m that is
+ * not a power of two or is below l, n_values >= 2^30, or a pp of another context: DG16_ERR_BAD_ARG, and nothing is
+ * written.  dg16_pss_scalar_chunks returns 0 for such arguments. */
+enum { DG16_PACK_CHUNKS = 0, DG16_PACK_DFFT = 1 };
+size_t dg16_pss_scalar_chunks(const dg16_pss *pp, int layout, size_t n_values);
+int dg16_pss_pack_scalars(dg16_ctx *ctx, const dg16_pss *pp, int layout, const void *values, size_t n_values,
+                          const void *blinds, void *shares);
+
+/* What a client sends for one proof, packed for all parties in one call: a, b, c (m = 2^log_m evaluations each) with
+ * DG16_PACK_DFFT (QAP::pss, qap.rs:151-165), full_assignment[1..] into a_share and full_assignment[num_inputs..] into
+ * ax_share with DG16_PACK_CHUNKS (sha256.rs:97-121).  Outputs party-major as above: a, b, c [n][m / l], a_share
+ * [n][ceil((num_vars - 1) / l)], ax_share [n][ceil((num_vars - num_inputs) / l)]; an empty vector writes nothing and its
+ * output may be NULL.
+ * seed32 == NULL packs plainly.  Otherwise every chunk is blinded as by dg16_pss_pack_scalars, and blind (e, k) of output
+ * v (0 .. 4 in the struct's order) is element e l + k of stream v of dg16_fr_expand, in the form `mont` names -- the form
+ * the inputs are in.  The blinds are made inside the packing kernel: they are never uploaded and never stored.  The seed
+ * is the CALLER's randomness: 32 uniform bytes, used for one request.
+ * Host pointers only.  Synchronous; runs on channel 0; slices and DG16_ERR_OOM as for dg16_pss_pack_scalars.  The five
+ * vectors are packed in the struct's order, each complete before the next begins.  2^log_m < l, log_m >= 30,
+ * num_inputs = 0, num_inputs > num_vars, num_vars >= 2^30, a NULL pointer or a pp of another context: DG16_ERR_BAD_ARG,
+ * checked before any work, and nothing is written. */
+typedef struct dg16_request_shares { void *a, *b, *c, *a_share, *ax_share; } dg16_request_shares;
+int dg16_request_pack(dg16_ctx *ctx, const dg16_pss *pp, unsigned log_m, const void *a, const void *b, const void *c,
+                      const void *full_assignment, size_t num_vars, size_t num_inputs, const void *seed32, int mont,
+                      const dg16_request_shares *out);
+
 /* share: this party's share_len packed shares; share_len * l must equal 2^log_m (the reference's
  * debug assertion, dfft/mod.rs:31-37) else DG16_ERR_BAD_ARG; out: pad * share_len elements. */
 int dg16_d_fft(dg16_ctx *ctx, const dg16_pss *pp, const dg16_net *net, const void *share,
