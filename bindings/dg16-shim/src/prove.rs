@@ -1,6 +1,7 @@
 //! The single-prover proof: `Groth16::<E, CircomReduction>::create_proof_with_reduction_and_matrices`
 //! (groth16/examples/sha256.rs:159, mpc-api/src/main.rs:393) as `dg16_qap` + `dg16_groth16_prove` over a key made
-//! resident once per circuit (`dg16_pk_create`).
+//! resident once per circuit (`dg16_pk_create`).  `E` is any pairing whose groups implement `Dg16Config`: `Bn254`,
+//! `Bls12_381` and `Bls12_377` (the curve of groth16/examples/local_groth_bench.rs) all have the resident prover.
 use crate::pack::{pack_affine, scalars_as_bytes, scalars_as_bytes_mut, unpack_projective, FieldBytes};
 use crate::{check, sys, Dg16Config, Dg16Error, CTX};
 use ark_ec::pairing::Pairing;

@@ -16,8 +16,29 @@ namespace dg16 {
   void assemble_##name(Call&, const uint8_t*, size_t, uint8_t*);                                                        \
   size_t results_bytes_##name();                                                                                        \
   size_t proof_bytes_##name();
-DECL_P(bn254) DECL_P(bls12_381)
+DECL_P(bn254) DECL_P(bls12_381) DECL_P(bls12_377)
 }  // namespace dg16
+
+// The ONE place that maps a curve id to its instantiation: `fn`_<curve>(args).  An id outside {0, 1, 2} throws
+// DG16_ERR_BAD_CURVE instead of falling into some curve's branch (a key's id was checked at dg16_pk_create).
+#define PROVER_DISPATCH(curve, fn, ...)                                                          \
+  do {                                                                                           \
+    switch (curve) {                                                                             \
+      case DG16_BN254: fn##_bn254(__VA_ARGS__); break;                                           \
+      case DG16_BLS12_381: fn##_bls12_381(__VA_ARGS__); break;                                   \
+      case DG16_BLS12_377: fn##_bls12_377(__VA_ARGS__); break;                                   \
+      default: DG_REQUIRE(false, DG16_ERR_BAD_CURVE, "Groth16: BN254, BLS12-381 or BLS12-377"); \
+    }                                                                                            \
+  } while (0)
+
+static size_t proof_bytes_of(int curve) {
+  switch (curve) {
+    case DG16_BN254: return dg16::proof_bytes_bn254();
+    case DG16_BLS12_381: return dg16::proof_bytes_bls12_381();
+    case DG16_BLS12_377: return dg16::proof_bytes_bls12_377();
+    default: return 0;
+  }
+}
 
 
 using namespace dg16;
@@ -39,8 +60,8 @@ int dg16_pk_create_shard(dg16_ctx* ctx, int curve, size_t num_vars, size_t num_i
   *out = nullptr;
   dg16_pk* pk = new dg16_pk{ctx, {}};
   int rc = guarded(ctx, [&] {
-    DG_REQUIRE(curve == DG16_BN254 || curve == DG16_BLS12_381, DG16_ERR_BAD_CURVE,
-               "Groth16 needs G2: BN254 or BLS12-381");
+    DG_REQUIRE(curve == DG16_BN254 || curve == DG16_BLS12_381 || curve == DG16_BLS12_377, DG16_ERR_BAD_CURVE,
+               "Groth16: BN254, BLS12-381 or BLS12-377");
     DG_REQUIRE(num_vars >= 2 && num_inputs >= 1 && num_inputs <= num_vars, DG16_ERR_BAD_ARG, "bad variable counts");
     DG_REQUIRE(domain_size && !(domain_size & (domain_size - 1)), DG16_ERR_BAD_ARG, "domain must be a power of two");
     DG_REQUIRE(a_query && b_g1_query && b_g2_query && h_query && l_query && fixed_points, DG16_ERR_BAD_ARG,
@@ -55,10 +76,7 @@ int dg16_pk_create_shard(dg16_ctx* ctx, int curve, size_t num_vars, size_t num_i
     pk->d.h_cyclic = (flags & DG16_F_H_CYCLIC) != 0;
     bool dev = flags & DG16_F_DEVICE_PTRS;
     if (dev) sync_channel0(ctx);   // pk_build copies the queries on the NULL stream: wait for their producers first
-    if (curve == DG16_BN254)
-      pk_build_bn254(ctx, pk->d, a_query, b_g1_query, b_g2_query, h_query, l_query, fixed_points, dev);
-    else
-      pk_build_bls12_381(ctx, pk->d, a_query, b_g1_query, b_g2_query, h_query, l_query, fixed_points, dev);
+    PROVER_DISPATCH(curve, pk_build, ctx, pk->d, a_query, b_g1_query, b_g2_query, h_query, l_query, fixed_points, dev);
   });
   if (rc != DG16_OK) {
     pk_free(pk->d);
@@ -103,15 +121,17 @@ int dg16_groth16_prove(dg16_ctx* ctx, const dg16_pk* pk, const void* a, const vo
     bool mont = flags & DG16_F_SCALARS_MONT, dev = flags & DG16_F_DEVICE_PTRS;
     const bool overlap = (flags & DG16_F_OVERLAP_TAIL) && dev;
     const bool libsnark = flags & DG16_F_QAP_LIBSNARK;
-    if (pk->d.curve == DG16_BN254)
-      prove_bn254(ctx, pk->d, a, b, c, full_assignment, r_s, mont, dev, proof_out, overlap, libsnark);
-    else
-      prove_bls12_381(ctx, pk->d, a, b, c, full_assignment, r_s, mont, dev, proof_out, overlap, libsnark);
+    PROVER_DISPATCH(pk->d.curve, prove, ctx, pk->d, a, b, c, full_assignment, r_s, mont, dev, proof_out, overlap, libsnark);
   });
 }
 
 size_t dg16_groth16_results_bytes(int curve) {
-  return curve == DG16_BN254 ? results_bytes_bn254() : curve == DG16_BLS12_381 ? results_bytes_bls12_381() : 0;
+  switch (curve) {
+    case DG16_BN254: return results_bytes_bn254();
+    case DG16_BLS12_381: return results_bytes_bls12_381();
+    case DG16_BLS12_377: return results_bytes_bls12_377();
+    default: return 0;
+  }
 }
 
 int dg16_groth16_msms(dg16_ctx* ctx, const dg16_pk* pk, const void* a, const void* b, const void* c,
@@ -127,10 +147,8 @@ int dg16_groth16_msms(dg16_ctx* ctx, const dg16_pk* pk, const void* a, const voi
     size_t rec = dg16_groth16_results_bytes(pk->d.curve);
     uint8_t* res_dev = dev ? (uint8_t*)results_out : (uint8_t*)ws(k0.c, 16, 8192);
     k0.begin_dominant();
-    if (pk->d.curve == DG16_BN254)
-      msms_bn254(ctx, k0, k1, k2, pk->d, a, b, c, full_assignment, r_s, mont, dev, res_dev, nullptr, nullptr);
-    else
-      msms_bls12_381(ctx, k0, k1, k2, pk->d, a, b, c, full_assignment, r_s, mont, dev, res_dev, nullptr, nullptr);
+    PROVER_DISPATCH(pk->d.curve, msms, ctx, k0, k1, k2, pk->d, a, b, c, full_assignment, r_s, mont, dev, res_dev, nullptr,
+                    nullptr);
     k0.end_dominant();
     if (!dev) stage_out(k0, results_out, res_dev, rec, false);
     k0.finish();
@@ -153,11 +171,8 @@ int dg16_groth16_msms_h(dg16_ctx* ctx, const dg16_pk* pk, const void* h_shard, c
     size_t rec = dg16_groth16_results_bytes(pk->d.curve);
     uint8_t* res_dev = dev ? (uint8_t*)results_out : (uint8_t*)ws(k0.c, 16, 8192);
     k0.begin_dominant();
-    if (pk->d.curve == DG16_BN254)
-      msms_bn254(ctx, k0, k1, k2, pk->d, nullptr, nullptr, nullptr, full_assignment, r_s, mont, dev, res_dev, nullptr, h_shard);
-    else
-      msms_bls12_381(ctx, k0, k1, k2, pk->d, nullptr, nullptr, nullptr, full_assignment, r_s, mont, dev, res_dev, nullptr,
-                     h_shard);
+    PROVER_DISPATCH(pk->d.curve, msms, ctx, k0, k1, k2, pk->d, nullptr, nullptr, nullptr, full_assignment, r_s, mont, dev,
+                    res_dev, nullptr, h_shard);
     k0.end_dominant();
     if (!dev) stage_out(k0, results_out, res_dev, rec, false);
     k0.finish();
@@ -178,10 +193,8 @@ int dg16_groth16_prove_dist(dg16_ctx* ctx, const dg16_pk* pk, const dg16_comm* c
     DG_REQUIRE(a_rows && b_rows && c_rows && full_assignment && r_s && proof_out, DG16_ERR_BAD_ARG, "null operand");
     bool mont = flags & DG16_F_SCALARS_MONT, dev = flags & DG16_F_DEVICE_PTRS;
     const bool overlap = (flags & DG16_F_OVERLAP_TAIL) && dev;
-    if (pk->d.curve == DG16_BN254)
-      prove_dist_bn254(ctx, pk->d, comm, a_rows, b_rows, c_rows, full_assignment, r_s, mont, dev, proof_out, overlap);
-    else
-      prove_dist_bls12_381(ctx, pk->d, comm, a_rows, b_rows, c_rows, full_assignment, r_s, mont, dev, proof_out, overlap);
+    PROVER_DISPATCH(pk->d.curve, prove_dist, ctx, pk->d, comm, a_rows, b_rows, c_rows, full_assignment, r_s, mont, dev,
+                    proof_out, overlap);
   });
 }
 
@@ -196,14 +209,8 @@ int dg16_groth16_assemble(dg16_ctx* ctx, const dg16_pk* pk, const void* gathered
     size_t rec = dg16_groth16_results_bytes(pk->d.curve);
     const uint8_t* g = (const uint8_t*)stage_in(k0, 19, gathered_results, n_shards * rec, dev);
     uint8_t* proof_dev = (uint8_t*)ws(k0.c, 16, 8192) + 4096;
-    size_t proof_bytes;
-    if (pk->d.curve == DG16_BN254) {
-      assemble_bn254(k0, g, n_shards, proof_dev);
-      proof_bytes = proof_bytes_bn254();
-    } else {
-      assemble_bls12_381(k0, g, n_shards, proof_dev);
-      proof_bytes = proof_bytes_bls12_381();
-    }
+    PROVER_DISPATCH(pk->d.curve, assemble, k0, g, n_shards, proof_dev);
+    const size_t proof_bytes = proof_bytes_of(pk->d.curve);
     stage_out(k0, proof_out, proof_dev, proof_bytes, dev);
     k0.finish();
     if (!dev) DG_HIP(hipStreamSynchronize(k0.s()));

@@ -424,7 +424,9 @@ int dg16_srs_verify(dg16_ctx *ctx, int curve, unsigned log_m, const dg16_srs_pow
  * | beta_g2 | delta_g2 (G2 affine), contiguous.  The base-vector mapping follows
  * groth16/src/proving_key.rs:48-65.  flags: DG16_F_DEVICE_PTRS if every pointer is a device pointer.
  * dg16_pk_create and dg16_pk_create_shard with DG16_F_DEVICE_PTRS: synchronous; ordered behind the work enqueued on
- * channel 0's stream; outputs complete on return (the key is resident and the queries may be freed or overwritten). */
+ * channel 0's stream; outputs complete on return (the key is resident and the queries may be freed or overwritten).
+ * curve: DG16_BN254, DG16_BLS12_381 or DG16_BLS12_377 -- the prover, its flags and its sharded forms are the same on all
+ * three (BLS12-377 proofs cannot be VERIFIED here: dg16_vk_create).  Any other id: DG16_ERR_BAD_CURVE, *out = NULL. */
 /* HBM budget, in bytes, of the window tables of ONE resident key (dg16_pk_create*: the five tables together) or ONE
  * base set (dg16_bases_upload) built on this context from now on; 0 (the default) = unlimited.  A full table has one
  * row T[w] = 2^(c w) P per c-bit window (BN254, 2^20 wires, c = 17: 6.0 GB per key; BLS12-381 at 2^24: 126 GB).  Under a
@@ -475,7 +477,8 @@ int dg16_groth16_prove(dg16_ctx *ctx, const dg16_pk *pk, const void *a, const vo
  *   <all-gather of the records over RCCL, done by the caller>
  *   dg16_groth16_assemble  per-MSM sum of the n_shards records + the A/B/C assembly of prove.rs:21-136
  * This is d_msm's "gather to king, sum, broadcast" (dist-primitives/src/dmsm/mod.rs:88-97) with the
- * sum done on every rank. */
+ * sum done on every rank.  dg16_groth16_results_bytes: bytes of one record (six G1 and one G2 Jacobian points: 768 for
+ * BN254, 1152 for BLS12-381 and BLS12-377), 0 for an unknown curve id. */
 size_t dg16_groth16_results_bytes(int curve);
 int dg16_groth16_msms(dg16_ctx *ctx, const dg16_pk *pk, const void *a, const void *b, const void *c,
                       const void *full_assignment, const void *r_s, unsigned flags, void *results_out);
