@@ -158,10 +158,21 @@ pub fn deg_red<F: PrimeField>(px: &[F], pp: &Pss, net: *const sys::Dg16Net, sid:
 
 /// `ext_wit::h` (groth16/src/ext_wit.rs:16-101): packed shares of the h-polynomial from the PackedQAPShare vectors.
 pub fn ext_wit_h<F: PrimeField>(a: &[F], b: &[F], c: &[F], log_m: u32, pp: &Pss, net: *const sys::Dg16Net) -> Result<Vec<F>, Dg16Error> {
+    ext_wit_h_flags(a, b, c, log_m, pp, net, 0)
+}
+
+/// `ext_wit::h` with the king keeping `s1[2 * i + 1]`, i < m (`DG16_F_H_ODD`): the packed sharing of CircomReduction's
+/// witness map at every packing factor, where [`ext_wit_h`] mirrors the reference's `s1.swap(i, i * l + t)` and is that
+/// at l = 2 alone.  Same rounds and message sizes; at l = 2 the same bytes.  Every party passes the same choice.
+pub fn ext_wit_h_odd<F: PrimeField>(a: &[F], b: &[F], c: &[F], log_m: u32, pp: &Pss, net: *const sys::Dg16Net) -> Result<Vec<F>, Dg16Error> {
+    ext_wit_h_flags(a, b, c, log_m, pp, net, sys::DG16_F_H_ODD)
+}
+
+fn ext_wit_h_flags<F: PrimeField>(a: &[F], b: &[F], c: &[F], log_m: u32, pp: &Pss, net: *const sys::Dg16Net, flags: c_uint) -> Result<Vec<F>, Dg16Error> {
     let mut out = vec![F::zero(); a.len()];
     check(unsafe {
         sys::dg16_ext_wit_h(CTX.0, pp.0, net, scalars_as_bytes(a).as_ptr().cast(), scalars_as_bytes(b).as_ptr().cast(),
-                            scalars_as_bytes(c).as_ptr().cast(), log_m, scalars_as_bytes_mut(&mut out).as_mut_ptr().cast(), 0)
+                            scalars_as_bytes(c).as_ptr().cast(), log_m, scalars_as_bytes_mut(&mut out).as_mut_ptr().cast(), flags)
     })?;
     Ok(out)
 }

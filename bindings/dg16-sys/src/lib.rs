@@ -35,6 +35,7 @@ pub const DG16_F_SERIAL_CHANNELS: c_uint = 16;
 pub const DG16_F_OVERLAP_TAIL: c_uint = 32;
 pub const DG16_F_BASES_IN_SUBGROUP: c_uint = 64;
 pub const DG16_F_QAP_LIBSNARK: c_uint = 128;
+pub const DG16_F_H_ODD: c_uint = 256; // dg16_ext_wit_h: the odd positions by rule, every l
 // enum dg16_field_opcode
 pub const DG16_OP_ADD: c_int = 0;
 pub const DG16_OP_SUB: c_int = 1;

@@ -588,8 +588,11 @@ int dg16_ext_wit_h(dg16_ctx* ctx, const dg16_pss* pp, const dg16_net* net, const
     DG_REQUIRE(m >= l, DG16_ERR_BAD_ARG, "domain smaller than the packing factor (m / l == 0)");
     // `s1.swap(i, i * pp.l + pp.t)` for i < m on a vector of 2m (ext_wit.rs:74-76) indexes past its end unless l <= 2:
     // the reference panics there.  Every party holds the same pp, so every party returns here, before any collective.
-    DG_REQUIRE((m - 1) * l + pp->t < 2 * m, DG16_ERR_UNSUPPORTED,
-               "ext_wit::h takes the odd positions of the unpacked evaluations: l <= 2 only, like the reference");
+    // DG16_F_H_ODD (one flags word per call, the same on every party) takes the odd positions by rule instead: any l.
+    const bool odd = flags & DG16_F_H_ODD;
+    DG_REQUIRE(odd || (m - 1) * l + pp->t < 2 * m, DG16_ERR_UNSUPPORTED,
+               "ext_wit::h takes the odd positions of the unpacked evaluations: l <= 2 only, like the reference "
+               "(DG16_F_H_ODD: every l)");
     bool dev = flags & DG16_F_DEVICE_PTRS;
     Call k(ctx, 0);
     FR_SWITCH(pp->curve, {
@@ -610,7 +613,13 @@ int dg16_ext_wit_h(dg16_ctx* ctx, const dg16_pss* pp, const dg16_net* net, const
       net_check(net->gather_to_king(net->self, 0, ev, 3 * 2 * mbyl * sizeof(Fr), gathered, k.s()));
       Fr* send = nullptr;
       Fr* dout = dev ? (Fr*)out : (Fr*)ws(k.c, 3, mbyl * sizeof(Fr));
-      if (king) {
+      if (king && odd) {
+        // h_i = p[2i+1] q[2i+1] - w[2i+1] straight from the gathered shares to the outgoing ones (h_king_kernel)
+        send = (Fr*)ws(k.c, 21, (size_t)n * mbyl * sizeof(Fr));
+        hipLaunchKernelGGL(h_king_kernel<Fr>, dim3(nblk(mbyl)), dim3(256), 0, k.s(), Dist<Fr>::mat(pp, 1),
+                           Dist<Fr>::mat(pp, 0), gathered, send, mbyl, l, n);
+        DG_HIP(hipGetLastError());
+      } else if (king) {
         Fr* un = (Fr*)ws(k.c, 19, 3 * 2 * m * sizeof(Fr));
         Fr* h = (Fr*)ws(k.c, 20, m * sizeof(Fr));
         send = (Fr*)ws(k.c, 21, (size_t)n * mbyl * sizeof(Fr));

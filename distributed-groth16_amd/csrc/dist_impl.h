@@ -15,6 +15,7 @@
 
 #include "ctx.h"
 #include "types.h"
+#include "h_odd.h"
 
 struct dg16_pss {
   dg16_ctx* ctx;
@@ -181,6 +182,49 @@ __global__ void __launch_bounds__(256) h_odd_kernel(const Fr* __restrict__ p, co
   if (i >= m) return;
   size_t s = i * l + t;
   h[i] = p[s] * q[s] - w[s];
+}
+
+// The king's whole step of dg16_ext_wit_h with DG16_F_H_ODD, one lane per output chunk c < m/l: unpack the odd
+// evaluations of packed elements 2c and 2c + 1 of p, q, w (h_odd.h says which element and row feed position i), h = p q - w,
+// apply the n pack rows, write send[party][c].  No unpacked buffer, no h buffer: the even evaluations are never formed.
+//   gathered  [n][3][2 mbyl]: party j's record holds its three vectors back to back
+//   U, P      unpack [l][n], pack [n][l] (dg16_pss::mats)
+// Per chunk 3 l n products for the unpack and n l for the pack: 4 m n in all, where three full unpacks, h_odd_kernel
+// and a pack take 7 m n.  Every sum runs in matvec_kernel's order (from zero, ascending column).
+// Reads: lane c touches gathered[j][v][2c], [2c + 1] <= 2 mbyl - 1; writes send[j * mbyl + c], c < mbyl.
+constexpr unsigned kMaxL = 8;
+template <class Fr>
+__global__ void __launch_bounds__(256) h_king_kernel(const Fr* __restrict__ U, const Fr* __restrict__ P,
+                                                      const Fr* __restrict__ gathered, Fr* __restrict__ send,
+                                                      size_t mbyl, unsigned l, unsigned n) {
+  size_t c = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (c >= mbyl) return;
+  const size_t vec = 2 * mbyl, rec = 3 * vec;
+  Fr h[kMaxL];
+#pragma unroll
+  for (unsigned i = 0; i < kMaxL; i++) {
+    if (i < l) {
+      const hodd::Source src = hodd::source(l, c, i);
+      const Fr* row = U + (size_t)src.row * n;
+      const Fr* g = gathered + src.elem;
+      Fr p = Fr::zero(), q = Fr::zero(), w = Fr::zero();
+      for (unsigned j = 0; j < n; j++) {
+        const Fr u = row[j];
+        const Fr* r = g + (size_t)j * rec;
+        p = p + u * r[0];
+        q = q + u * r[vec];
+        w = w + u * r[2 * vec];
+      }
+      h[i] = p * q - w;
+    }
+  }
+  for (unsigned j = 0; j < n; j++) {
+    Fr acc = Fr::zero();
+#pragma unroll
+    for (unsigned i = 0; i < kMaxL; i++)
+      if (i < l) acc = acc + P[j * l + i] * h[i];
+    send[(size_t)j * mbyl + c] = acc;
+  }
 }
 
 // batched inverse + exclusive structure for d_pp: numden[i] = num[i] * den[i]^-1 (dpp/mod.rs:58-61)

@@ -16,7 +16,7 @@ import threading
 
 import numpy as np
 
-from .lib import CURVES, FQ_LIMBS64, Context, load, _ptr  # noqa: F401
+from .lib import CURVES, FQ_LIMBS64, F_H_ODD, Context, load, _ptr  # noqa: F401
 
 
 class PackedSharingParams:
@@ -218,8 +218,13 @@ def d_pp(ctx, pp, net, num, den, sid=0):
     return out
 
 
-def ext_wit_h(ctx, pp, net, a_share, b_share, c_share, log_m):
+def ext_wit_h(ctx, pp, net, a_share, b_share, c_share, log_m, odd=False):
+    """odd: DG16_F_H_ODD -- the king keeps the odd positions of the unpacked evaluations by rule, so the result is the
+    packed sharing of CircomReduction's witness map at every l.  The default mirrors the reference's swap: the witness
+    map at l = 2 only, the first m evaluations at l = 1, DG16_ERR_UNSUPPORTED at l = 4, 8.  Every party of a call
+    passes the same value."""
     a, b, c = _fr(a_share), _fr(b_share), _fr(c_share)
     out = np.zeros_like(a)
-    ctx._chk(ctx.L.dg16_ext_wit_h(ctx.h, pp.h, net, _ptr(a), _ptr(b), _ptr(c), log_m, _ptr(out), 0))
+    ctx._chk(ctx.L.dg16_ext_wit_h(ctx.h, pp.h, net, _ptr(a), _ptr(b), _ptr(c), log_m, _ptr(out),
+                                  F_H_ODD if odd else 0))
     return out

@@ -198,15 +198,16 @@ class C:
 
 
 def party_prove(ctx, pp, net, crs_share, qap_share, a_share, ax_share, log_m, r=None, s=None, L=None, N=None,
-                Z=None, K=None, M=None, serial_channels=False):
+                Z=None, K=None, M=None, serial_channels=False, h_odd=False):
     """One party of the reference's example (`dsha256`, groth16/examples/sha256.rs:26-95): h = ext_wit::h, then
     A::compute, B::compute, C::compute exactly as there.  The example passes r = s = 0 and Default points
     (:46-48, :60-62, :77-79) -- the defaults here; any other values go through the same native entry points.
-    Returns (pi_a, pi_b, pi_c) Jacobian, identical on all parties."""
+    h_odd: dist.ext_wit_h's `odd` (DG16_F_H_ODD) -- needed for a proof at l = 1, 4, 8 (4, 16, 32 parties); at l = 2 the
+    same bytes either way.  Returns (pi_a, pi_b, pi_c) Jacobian, identical on all parties."""
     zero = np.zeros((1, 4), dtype=np.uint64)
     r = zero if r is None else r
     s = zero if s is None else s
-    h_share = D.ext_wit_h(ctx, pp, net, qap_share[0], qap_share[1], qap_share[2], log_m)     # :41
+    h_share = D.ext_wit_h(ctx, pp, net, qap_share[0], qap_share[1], qap_share[2], log_m, odd=h_odd)     # :41
     pi_a = A(L, N, r, pp, crs_share["s"], a_share).compute(ctx, net, 0)                      # :45-57
     pi_b = B(Z, K, s, pp, crs_share["v"], a_share).compute(ctx, net, 0)                      # :59-71
     pi_c = C(pi_a, M, s, r, pp, crs_share["w"], crs_share["u"], crs_share["h"], a_share, ax_share,

@@ -23,6 +23,7 @@ F_SERIAL_CHANNELS = 16
 F_OVERLAP_TAIL = 32
 F_BASES_IN_SUBGROUP = 64
 F_QAP_LIBSNARK = 128
+F_H_ODD = 256
 
 REDUCTIONS = {"circom": 0, "libsnark": F_QAP_LIBSNARK}
 

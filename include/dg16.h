@@ -99,10 +99,13 @@ enum dg16_flags {
                                (BN254 G1) take that path and every other group runs plain Pippenger, which -- like
                                VariableBaseMSM::msm -- is correct for ANY point of the curve.  Resident keys / tables
                                (dg16_pk_create*, dg16_bases_upload) never split and ignore the flag. */
-  DG16_F_QAP_LIBSNARK = 128u /* dg16_h_poly, dg16_groth16_setup, dg16_groth16_prove: the Libsnark QAP reduction instead of the
+  DG16_F_QAP_LIBSNARK = 128u, /* dg16_h_poly, dg16_groth16_setup, dg16_groth16_prove: the Libsnark QAP reduction instead of the
                                circom one (see "The two QAP reductions" below).  Without the flag every call is unchanged.
                                The sharded entry points (dg16_groth16_msms, dg16_groth16_msms_h, dg16_groth16_prove_dist,
                                dg16_h_poly_dist, dg16_h_poly_dist_stage) return DG16_ERR_UNSUPPORTED with it. */
+  DG16_F_H_ODD = 256u /* dg16_ext_wit_h only: the king keeps the ODD positions of the 2m unpacked evaluations, whatever l is
+                         -- CircomReduction's witness map at l = 1, 2, 4, 8 -- instead of mirroring the reference's swap,
+                         which does that at l = 2 alone (see dg16_ext_wit_h).  Without the flag the call is unchanged. */
 };
 
 /* field ids for dg16_field_op: curve for the base field Fq, 16 + curve for the scalar field Fr */
@@ -625,7 +628,8 @@ void dg16_localnet_abort(dg16_localnet *net);
 void dg16_localnet_reset(dg16_localnet *net, unsigned timeout_s);
 
 /* l: the packing factor, 1, 2, 4 or 8 (n = 4 l = 4, 8, 16 or 32 parties, t = l - 1); anything else is
- * DG16_ERR_BAD_ARG.  Every primitive below takes every accepted l except dg16_ext_wit_h (see there). */
+ * DG16_ERR_BAD_ARG.  Every primitive below takes every accepted l; dg16_ext_wit_h does with
+ * DG16_F_H_ODD (see there). */
 int dg16_pss_create(dg16_ctx *ctx, int curve, unsigned l, dg16_pss **out);
 void dg16_pss_destroy(dg16_pss *pp);
 /* which: 0 pack ([count][l] -> [count][n]), 1 unpack ([count][n] -> [count][l]), 2 unpack2 */
@@ -747,14 +751,25 @@ int dg16_deg_red(dg16_ctx *ctx, const dg16_pss *pp, const dg16_net *net, const v
 int dg16_d_pp(dg16_ctx *ctx, const dg16_pss *pp, const dg16_net *net, const void *num, const void *den,
               size_t count, void *out, unsigned flags, int channel);
 /* a/b/c_share: this party's PackedQAPShare vectors (m/l each); out: m/l packed shares of h.
- * Uses channel 0 (the reference multiplexes channels 0..2 for the three transforms).
- * l <= 2 only, as in the reference: its `s1.swap(i, i * pp.l + pp.t)` for i < m on the 2m unpacked evaluations
- * (ext_wit.rs:74-76) indexes past the vector for l = 4 or 8 and panics; here those l return DG16_ERR_UNSUPPORTED.
- * 2^log_m < l, log_m >= 48 and net.n_parties() != pp.n are DG16_ERR_BAD_ARG.  All three are decided from pp and log_m alone, before
- * any collective: every party gets the same code and nobody waits.
- * At l = 2 the result is the packed sharing of CircomReduction's witness map.  At l = 1 (t = 0) the swap is the
- * identity, so the reference keeps the FIRST m of the 2m evaluations, not the odd ones: the call mirrors that output
- * share for share, and it is NOT the witness map. */
+ * Uses channel 0 (the reference multiplexes channels 0..2 for the three transforms).  Six transform rounds (d_ifft
+ * padded to 2m, d_fft on 2m, for each of a, b, c), then one gather of 3 * 2m/l shares and one scatter of m/l.
+ * 2^log_m < l, log_m >= 48 and net.n_parties() != pp.n are DG16_ERR_BAD_ARG with and without the flag below.  Every
+ * refusal is decided from pp, log_m and flags alone, before any collective: every party gets the same code and nobody
+ * waits.
+ *
+ * Without DG16_F_H_ODD: the reference's ext_wit::h, share for share, its defect included.  The king's selection there
+ * is `s1.swap(i, i * pp.l + pp.t)` for i < m on the 2m unpacked evaluations (ext_wit.rs:74-76).
+ *   l = 2     keeps the odd positions: the packed sharing of CircomReduction's witness map.
+ *   l = 4, 8  indexes past the vector and panics; here DG16_ERR_UNSUPPORTED.
+ *   l = 1     (t = 0) the swap is the identity, so the FIRST m evaluations are kept, not the odd ones: the call mirrors
+ *             that output, and it is NOT the witness map.
+ *
+ * With DG16_F_H_ODD: what the reference meant.  Same rounds, same channel, same message sizes; the king computes
+ * h_i = p[2i+1] q[2i+1] - w[2i+1], i < m, over the natural-order unpacked evaluations, packs consecutive l-chunks
+ * (pack_vec, utils/pack.rs:4-16) and scatters m/l shares per party.  The output is the packed sharing of
+ * CircomReduction's witness map for l = 1, 2, 4, 8, and at l = 2 it is byte-equal to the unflagged call.  A Rust party
+ * whose selection reads `s1[i] = s1[2 * i + 1]` interoperates.  The king forms only the odd-position secrets, in one
+ * kernel (csrc/h_odd.h). */
 int dg16_ext_wit_h(dg16_ctx *ctx, const dg16_pss *pp, const dg16_net *net, const void *a_share,
                    const void *b_share, const void *c_share, unsigned log_m, void *out, unsigned flags);
 /* prove::A::compute (groth16/src/prove.rs:21-46): out = L + N * r + d_msm(S, a) on `channel` (the reference's `sid`).
